@@ -12,22 +12,29 @@ the hot path, from the first event append to the order in host memory (SURVEY §
     in one call (Bootstrap, hashgraph.go:1008-1037); the payload columns (timestamps, hash, S,
     transactions) are copied while DivideRounds runs
 
-Side legs on the same line: the step with the columns already in HBM (hbm_resident), the
-SyncLimit-chunked schedule (chunked_sync), event ids (ingest_sha256), signature checks
-(ingest_p256_verify), and the InsertEvent pass with Event.Verify (insert_verify).
+A plain run does what the headline needs and no more: it builds the trace, warms up, times
+--steps steps and prints the line (metric, value, ms_per_step, the configuration). With
+--dump-outputs DIR it also writes what the last timed step computed (rounds, witnesses, fame,
+rounds received, consensus timestamps, the order) as DIR/<name>.npy, see dump_outputs().
 
-After the timed steps (outside the clock) the run is checked: the GPU against the CPU oracle
-on a prefix of the same trace (every output, bit-exact), and the full-size result against
-the order properties the reference guarantees (a permutation of the received events sorted
-by (round received, consensus timestamp, S), rounds monotone along every chain, blocks
-consistent). A failed check exits non-zero without a result line.
+--full adds the rest to the same line. Before the timed steps, one pass with every kernel timed
+ranks the kernels (kernels_per_pass), and the dominant one stays instrumented in the timed steps
+(roofline). Side legs: the step with the columns already in HBM (hbm_resident), the packed
+columns (packed_columns), the SyncLimit-chunked schedule (chunked_sync), event ids
+(ingest_sha256), signature checks (ingest_p256_verify), and the InsertEvent pass with
+Event.Verify (insert_verify). After the timed steps (outside the clock) the run is checked: the
+GPU against the CPU oracle on a prefix of the same trace (every output, bit-exact; the oracle's
+time on it is the cpu_baseline), and the full-size result against the order properties the
+reference guarantees (a permutation of the received events sorted by (round received, consensus
+timestamp, S), rounds monotone along every chain, blocks consistent). A failed check exits
+non-zero without a result line.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c1|c2|c4|c5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c1|c2|c4|c5] [--full] [--dump-outputs DIR]
   (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N; without a launcher,
   --gpus N > 1 starts that launcher itself as a child process before any GPU call and exits with
   its status, so the line always carries N ranks' work)
 
-At N > 1 the line also carries `sharded`: C3's single-graph mode (one graph whose round recurrence is
+At N > 1 the --full line also carries `sharded`: C3's single-graph mode (one graph whose round recurrence is
 chain-sharded over all N devices, hgx_create_sharded) timed by rank 0 in a child process
 after every rank has released its GPU memory (the other ranks wait on the host).
 """
@@ -253,6 +260,57 @@ def full_size_checks(h, tr, G):
                            "round non-decreasing along every chain", "received events form a chain prefix",
                            "rr non-decreasing along chains", "rr > round", "witness iff round > round(sp)",
                            "blocks: one per rr, cover the order, transaction totals"], "result": "pass"}
+
+
+DUMP_SAMPLE = 1 << 20   # rows of a per-event array that --dump-outputs writes (9 arrays, 56 MB at most)
+
+
+def dump_outputs(h, G, out_dir):
+    """--dump-outputs: what the last timed step left for its caller, read back through the C ABI
+    as the caller would (hgx_get_rounds, hgx_get_received, hgx_consensus_events and the Store
+    counters) and written as <name>.npy in float32/float64, every value exact: rounds fit float32,
+    event ids float64, the int64 consensus timestamps are split into their high and low 32 bits.
+    Per-event arrays longer than DUMP_SAMPLE are written at a fixed seeded sample of the events
+    (event_sample) and of the positions of the consensus order (order_sample); `checksums` covers
+    the arrays in full (position-weighted sums modulo 2^52). The trace is seeded, so two runs with
+    the same arguments write the same files."""
+    def sample(count, seed):
+        if count <= DUMP_SAMPLE:
+            return np.arange(count)
+        return np.sort(np.random.default_rng(seed).choice(count, DUMP_SAMPLE, replace=False))
+
+    def checksum(a):
+        a = np.asarray(a).astype(np.int64).view(np.uint64)
+        w = (np.arange(len(a), dtype=np.uint64) % np.uint64(65521)) + np.uint64(1)
+        return float(int((a * w).sum(dtype=np.uint64)) % (1 << 52))   # (uint64 arithmetic wraps)
+
+    rnd, wit, fam = h.rounds()
+    rr, cts = h.received()
+    cts = np.where(rr >= 0, cts, 0)   # (defined for received events only)
+    orders = [h.ConsensusEvents(g) for g in range(G)]
+    order = np.concatenate(orders) if orders else np.zeros(0, np.int64)
+    ev, pos = sample(len(rnd), 20240601), sample(len(order), 20240602)
+    lcr = [h.LastConsensusRound(g) for g in range(G)]
+    arrays = {
+        "event_sample": ev.astype(np.float64),
+        "round": rnd[ev].astype(np.float32),
+        "witness": wit[ev].astype(np.float32),
+        "famous": fam[ev].astype(np.float32),
+        "round_received": rr[ev].astype(np.float32),
+        "consensus_timestamp_hi32": (cts[ev] >> 32).astype(np.float64),
+        "consensus_timestamp_lo32": (cts[ev] & 0xFFFFFFFF).astype(np.float64),
+        "order_sample": pos.astype(np.float64),
+        "order": order[pos].astype(np.float64),
+        "per_graph": np.array([[len(orders[g]), h.LastRound(g), -1 if lcr[g] is None else lcr[g],
+                                h.LastCommitedRoundEvents(g), h.ConsensusTransactions(g), len(h.Blocks(g))]
+                               for g in range(G)], np.float64),
+        "checksums": np.array([len(rnd), len(order)] + [checksum(a) for a in (rnd, wit, fam, rr, cts, order)],
+                              np.float64),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "arrays": sorted(arrays), "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 class Reducer:
@@ -582,12 +640,14 @@ def run_sharded(args):
         tw = time.time()
         ordered = step()
         log(f"[sharded x{len(devs)}] warmup {w}: {ordered} ordered in {time.time() - tw:.2f}s  {h.phase_times()}")
-    # shard 0's kernels on one untimed pass (HIP events on its stream)
-    h.set_kernel_timing(True)
-    h.reset_stats()
-    step()
-    ks_w = h.kernel_stats()
-    h.set_kernel_timing(False)
+    ks_w = {}
+    if args.full:
+        # shard 0's kernels on one untimed pass (HIP events on its stream)
+        h.set_kernel_timing(True)
+        h.reset_stats()
+        step()
+        ks_w = h.kernel_stats()
+        h.set_kernel_timing(False)
     t0 = time.perf_counter()
     ordered = 0
     for _ in range(args.steps):
@@ -596,8 +656,9 @@ def run_sharded(args):
     ph = h.phase_times()
     if ph["round_p_fallbacks"]:
         raise SystemExit(f"--sharded: the sharded recurrence fell back to per-launch steps: {ph}")
+    dumped = dump_outputs(h, 1, args.dump_outputs) if args.dump_outputs else None
     checks = {"full_size": "skipped"}
-    if not args.no_check:
+    if args.full and not args.no_check:
         checks["full_size"] = full_size_checks(h, tr, 1)
     rounds = int(h.LastRound()) + 1
     rs = ks_w.get("round_search", {"ms": 0.0, "launches": 0})
@@ -617,7 +678,7 @@ def run_sharded(args):
                    "phase_ms_last_step": {k: round(float(v), 3) for k, v in ph.items()}},
         "rounds": rounds,
         "kernels_shard0_ms": {k: round(v["ms"], 4) for k, v in ks_w.items()},
-        "checks": checks}
+        "checks": checks, "full": bool(args.full)}
     if rs["ms"] > 0:
         b = kernel_bytes("round_search", n, tr.E, 0, ph["compact"])
         ach = b / (rs["ms"] * 1e-3) / 1e9
@@ -626,7 +687,9 @@ def run_sharded(args):
                             "ms_per_pass": rs["ms"], "algorithmic_bytes_per_pass": b,
                             "note": "shard 0's k_round_p launch (its chain block; every shard's launch spans the "
                                     "whole recurrence, the rounds are shared)"}
-    if not args.no_cpu_baseline:
+    if dumped:
+        line["outputs"] = dumped
+    if args.full and not args.no_cpu_baseline:
         sample = min(E, SAMPLE.get(n, 20000))
         ts = trace.gossip(n, sample, 1, n_silent=silent, stale_prob=stale, stale_depth=depth)
         line["cpu_baseline"], _ = cpu_baseline(ts, n, desc)
@@ -655,7 +718,7 @@ def sharded_leg(args, world):
     if per_dev > 1:   # shards sharing a device need a hardware queue each (hgx_create_sharded)
         env["GPU_MAX_HW_QUEUES"] = str(max(int(env.get("GPU_MAX_HW_QUEUES", "4")), per_dev + 4))
     cmd = [sys.executable, os.path.abspath(__file__), "--sharded", "--gpus", str(world), "--config", args.config,
-           "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-cpu-baseline"]
+           "--steps", str(args.steps), "--warmup", str(args.warmup), "--full", "--no-cpu-baseline"]
     if args.no_check:
         cmd.append("--no-check")
     t0 = time.time()
@@ -738,6 +801,13 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the per-kernel pass and rooflines, the side legs, the full-size checks, "
+                         "the CPU baseline and prefix parity, and at N > 1 the sharded leg (the --no-* switches "
+                         "drop single legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32/float64; a fixed seeded sample of the per-event arrays above 1 Mi events)")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle leg (and the prefix parity check)")
     ap.add_argument("--no-ingest", action="store_true", help="skip the batched event-id SHA-256 side leg")
     ap.add_argument("--no-check", action="store_true", help="skip the full-size property checks")
@@ -770,6 +840,8 @@ def main():
     ap.add_argument("--round-shards", type=int, default=1,
                     help="the chain-sharded recurrence with W shards on this rank's GPU (measurement)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
     if args.sharded or args.round_shards > 1:
         # shards that share a device need a hardware queue each (their launches wait for each
         # other): set before the HIP runtime starts
@@ -849,20 +921,20 @@ def main():
         tw = time.time()
         ordered = step()
         log(f"[rank {rank}] warmup {w}: {ordered} ordered in {time.time() - tw:.2f}s  {h.phase_times()}")
-    # the kernels ranked on one post-warmup pass with every launch timed (HIP events on the
-    # context stream; no first-touch costs): the per-kernel table and the dominant kernel
-    h.set_kernel_timing(True)
-    h.reset_stats()
-    step()
-    ks_w, nw = h.kernel_stats(), 1
-    dom = max(ks_w, key=lambda k: ks_w[k]["ms"])
-    log(f"[rank {rank}] kernel profile (ms per pass / launches): " +
-        ", ".join(f"{k}={v['ms'] / nw:.2f}/{v['launches'] // nw}" for k, v in
-                  sorted(ks_w.items(), key=lambda kv: -kv[1]['ms'])))
-
-    # timed region: the dominant kernel alone is instrumented
-    h.set_kernel_timing(dom)
-    h.reset_stats()
+    if args.full:
+        # the kernels ranked on one post-warmup pass with every launch timed (HIP events on the
+        # context stream; no first-touch costs): the per-kernel table and the dominant kernel
+        h.set_kernel_timing(True)
+        h.reset_stats()
+        step()
+        ks_w, nw = h.kernel_stats(), 1
+        dom = max(ks_w, key=lambda k: ks_w[k]["ms"])
+        log(f"[rank {rank}] kernel profile (ms per pass / launches): " +
+            ", ".join(f"{k}={v['ms'] / nw:.2f}/{v['launches'] // nw}" for k, v in
+                      sorted(ks_w.items(), key=lambda kv: -kv[1]['ms'])))
+        # timed region: the dominant kernel alone is instrumented
+        h.set_kernel_timing(dom)
+        h.reset_stats()
     red.barrier()
     t_start = time.perf_counter()   # every hgx call returns with its work complete (order in host memory)
     total = 0
@@ -872,8 +944,56 @@ def main():
     red.barrier()
     t_max = red.max(t_el)
     total_all = red.sum(total)
-    ks = h.kernel_stats()
     phases = h.phase_times()
+    m_pass = total // args.steps
+    # the headline: everything a plain run reports (--full adds its legs to the same line)
+    head = {
+        "metric": "consensus-ordered events/sec at N=256 peers (1 GPU and 8-GPU batched sims)",
+        "value": total_all / t_max,
+        "unit": "consensus-ordered events/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": t_max * 1e3 / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int32",
+        "data": "synthetic (seeded random-gossip traces, synthetic event ids/signatures), in host RAM at "
+                "the start of every step (hgx_insert_events copies the columns to HBM inside the step)",
+        "config": {"workload": CONFIGS[args.config][6], "config": args.config, "peers": n,
+                   "events_per_gpu": int(tr.E), "graphs_per_gpu": G,
+                   "ordered_events_per_step_per_gpu": int(m_pass),
+                   "step": ("clear + hgx_insert_and_run" +
+                            {"wide": "", "compact": "32", "packed": "_packed"}[args.columns] +
+                            ": InsertEvent (H2D of the event columns + device validation) + DivideRounds + "
+                            "DecideFame + FindOrder, the payload columns' H2D beside DivideRounds; order in "
+                            "host memory"),
+                   "host_columns": {
+                       "wide": "hgx_events (108 B/event)",
+                       "compact": "hgx_events32 (int32 Index/parents, coin byte, ntx -1 = nil: 61 B/event)",
+                       "packed": "hgx_events_packed (u16 creator, int32 Index, u16 parent distances: 10 B "
+                                 "structure + 45 B payload per event; %d exceptions)" % (
+                                     len(pk["exc_pos"]) if pk is not None else 0)}[args.columns],
+                   "host_memory": args.host_memory if cols is not None else "pageable",
+                   "parallelism": f"replicas x{world} (seed-sharded)" +
+                                  (f"; recurrence rehearsed in {args.round_shards} chain blocks on one GPU"
+                                   if args.round_shards > 1 else ""),
+                   "phase_ms_last_step": {k: round(float(v), 3) for k, v in phases.items()}},
+        "full": bool(args.full),
+    }
+    if args.dump_outputs and rank == 0:
+        td = time.time()
+        head["outputs"] = dump_outputs(h, G, args.dump_outputs)
+        log(f"[rank {rank}] outputs of the last timed step written to {args.dump_outputs} in {time.time() - td:.1f}s")
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        h.close()
+        if red.dist is not None:
+            red.dist.destroy_process_group()
+        return 0
+    ks = h.kernel_stats()
     h.set_kernel_timing(False)
 
     # side leg: the same step with the event columns already resident in HBM (no H2D)
@@ -970,40 +1090,9 @@ def main():
                                       "64 lanes per wave instruction, over this line's ms_per_pass)"}
             except Exception:
                 valu = None
+        head["config"]["dominant_kernel"] = dom
         result = {
-            "metric": "consensus-ordered events/sec at N=256 peers (1 GPU and 8-GPU batched sims)",
-            "value": total_all / t_max,
-            "unit": "consensus-ordered events/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": t_max * 1e3 / args.steps,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "int32",
-            "data": "synthetic (seeded random-gossip traces, synthetic event ids/signatures), in host RAM at "
-                    "the start of every step (hgx_insert_events copies the columns to HBM inside the step)",
-            "config": {"workload": CONFIGS[args.config][6], "config": args.config, "peers": n,
-                       "events_per_gpu": int(tr.E), "graphs_per_gpu": G,
-                       "ordered_events_per_step_per_gpu": int(m_pass),
-                       "step": ("clear + hgx_insert_and_run" +
-                                {"wide": "", "compact": "32", "packed": "_packed"}[args.columns] +
-                                ": InsertEvent (H2D of the event columns + device validation) + DivideRounds + "
-                                "DecideFame + FindOrder, the payload columns' H2D beside DivideRounds; order in "
-                                "host memory"),
-                       "host_columns": {
-                           "wide": "hgx_events (108 B/event)",
-                           "compact": "hgx_events32 (int32 Index/parents, coin byte, ntx -1 = nil: 61 B/event)",
-                           "packed": "hgx_events_packed (u16 creator, int32 Index, u16 parent distances: 10 B "
-                                     "structure + 45 B payload per event; %d exceptions)" % (
-                                         len(pk["exc_pos"]) if pk is not None else 0)}[args.columns],
-                       "host_memory": args.host_memory if cols is not None else "pageable",
-                       "parallelism": f"replicas x{world} (seed-sharded)" +
-                                      (f"; recurrence rehearsed in {args.round_shards} chain blocks on one GPU"
-                                       if args.round_shards > 1 else ""),
-                       "phase_ms_last_step": {k: round(float(v), 3) for k, v in phases.items()},
-                       "dominant_kernel": dom},
+            **head,
             "roofline": {"kernel": dom, "bound": BOUND.get(dom, "hbm"), "achieved": achieved, "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                          "ms_per_pass": dom_ms, "launches_per_pass": r["launches"] // max(1, args.steps),

@@ -27,7 +27,7 @@ def test_bench_replicas_world2(cfg):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes", "1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--config", cfg, "--backend", "gloo", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-ingest", "--no-chunked"]
+           "--full", "--no-cpu-baseline", "--no-ingest", "--no-chunked"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=200)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -48,7 +48,7 @@ def test_bench_self_launch_and_sharded_leg(cfg):
     chain-sharded over the N devices (both shards on the box's one GPU here) -- with no fallback and the
     full-size checks passing."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", cfg, "--steps", "2",
-           "--warmup", "1", "--no-cpu-baseline", "--no-ingest", "--no-chunked"]
+           "--warmup", "1", "--full", "--no-cpu-baseline", "--no-ingest", "--no-chunked"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -2,7 +2,7 @@
 
 * C3-shaped: 256 peers, 200k events (chains ~780 long, 57 rounds), compact uint16
   coordinates, the n <= 256 round step, k_cts_tile at n = 256 -- every output against the
-  oracle (the oracle needs ~1 min here; bench.py adds the full-size property checks).
+  oracle (the oracle needs ~1 min here; bench.py --full adds the full-size property checks).
 * Timestamps so far apart that the (graph, rr, cts - min) sort key needs more than 64 bits
   (two-pass sort, hgx_engine.cpp find_order) and the consensus-timestamp offsets overflow
   32 bits (k_cts_tile's 64-bit reselect), alone and mixed with ordinary events.

@@ -260,7 +260,7 @@ def test_bench_sharded_line():
     import json
     root = os.path.dirname(HERE)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--sharded", "--gpus", "2", "--config", "c2",
-                        "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=300, cwd=root)
+                        "--steps", "2", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=300, cwd=root)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["shards"] == 2 and line["scaling"] == "strong" and line["value"] > 0, line
