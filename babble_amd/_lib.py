@@ -47,6 +47,12 @@ class hgx_events_packed(C.Structure):
                                             "sig_s", "ntx")]
 
 
+class hgx_event_bodies(C.Structure):
+    _fields_ = [(nm, C.c_void_p) for nm in
+                ("creator", "index", "self_parent", "other_parent", "timestamp_ns", "sig_r", "sig_s", "ntx",
+                 "tx_off", "tx_bytes")]
+
+
 class hgx_wire_events(C.Structure):
     _fields_ = [(nm, C.c_void_p) for nm in
                 ("creator_id", "index", "self_parent_index", "other_parent_creator", "other_parent_index",
@@ -122,6 +128,9 @@ def lib():
     _sig(L, "hgx_set_participant_keys", i32, [p, p, E])
     for nm in ("hgx_insert_events_verified", "hgx_insert_events_verified_device"):
         _sig(L, nm, i32, [p, C.POINTER(hgx_events), p, p, i64, C.POINTER(C.c_int64), E])
+    _sig(L, "hgx_insert_event_bodies", i32, [p, C.POINTER(hgx_event_bodies), i64, p, C.POINTER(C.c_int64), E])
+    _sig(L, "hgx_event_json_batch", i32, [i32, C.POINTER(hgx_event_bodies), i64, p, i32, p, p, p, i64, p, E])
+    _sig(L, "hgx_batch_levels", i32, [p, p, i64, i64, p, C.POINTER(C.c_int32), E])
     _sig(L, "hgx_reset_consensus", i32, [p])
     _sig(L, "hgx_save", i32, [p, C.c_char_p, E])
     _sig(L, "hgx_save_ex", i32, [p, C.c_char_p, p, p, E])

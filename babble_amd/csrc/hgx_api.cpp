@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "hgx.h"
+#include "hgx_bodies.h"
 #include "hgx_engine.h"
 
 namespace {
@@ -847,6 +848,50 @@ int32_t hgx_insert_events_verified(hgx_ctx* c, const hgx_events* ev, const uint8
 int32_t hgx_insert_events_verified_device(hgx_ctx* c, const hgx_events* ev, const uint8_t* digest32,
                                           const uint8_t* sig_r32, int64_t count, int64_t* n_inserted, hgx_error* err) {
     return insert_verified(c, ev, digest32, sig_r32, count, n_inserted, err, true);
+}
+
+// InsertEvent with Event.Hash and Event.Verify on the device, from the events' fields (DESIGN.md
+// §3.10). An event without a text (creator without a key, a parent that is neither "" nor an earlier
+// gid) cuts the batch: the prefix goes through the body path, then that event through the plain insert
+// checks, which reject it with the reference's parent-check error.
+int32_t hgx_insert_event_bodies(hgx_ctx* c, const hgx_event_bodies* evb, int64_t count, uint8_t* out_id32,
+                                int64_t* n_inserted, hgx_error* err) {
+    const std::string who = "hgx_insert_event_bodies: ";
+    auto bad = [&](const std::string& why) {
+        set_err(err, HGX_ERR_INVALID, who + why);
+        return (int32_t)HGX_ERR_INVALID;
+    };
+    if (n_inserted) *n_inserted = 0;
+    if (!evb || count < 0) return bad("bad arguments");
+    const hgx::BodiesIn ev{evb->creator, evb->index, evb->self_parent, evb->other_parent, evb->timestamp_ns,
+                           evb->sig_r, evb->sig_s, evb->ntx, evb->tx_off, evb->tx_bytes};
+    std::vector<int64_t> txi;
+    if (const char* why = hgx::bodies_check(ev, count, txi)) return bad(why);
+    if (!c) return bad("bad arguments");
+    if (c->grp) return bad("not available on a chain-sharded context");
+    if (c->shard_world > 1) return bad("not available on a row-sharded context");
+    if (c->rooted) return bad("not after hgx_reset (a Root's events have no id in the store)");
+    if (!c->eng.keys_set) return bad("participant keys not set");
+    if (!c->eng.ids_known) return bad("ids not known (the context holds events inserted without their ids)");
+    DeviceGuard dg(c);
+    const int64_t cut = hgx::bodies_first_unencodable(ev, count, c->E, c->C);
+    hgx::InsertOut out;
+    hipError_t e = c->eng.insert_bodies(ev, txi, cut, out_id32, out);
+    if (e != hipSuccess) return dev_err(err, e, "hgx_insert_event_bodies");
+    if (out.code == hgx::INS_OK && cut < count) {
+        // the cut event's own checks (it cannot pass them: its creator or a parent is unknown)
+        const int64_t ok_before = out.accepted;
+        const uint8_t zero[32] = {};
+        const int32_t ntx = evb->ntx[cut] < 0 ? 0 : evb->ntx[cut], nil = evb->ntx[cut] < 0 ? 1 : 0;
+        hgx::InsertIn in{};
+        e = c->eng.stage_host(ev.creator + cut, ev.index + cut, ev.sp + cut, ev.op + cut, ev.ts + cut, zero,
+                              ev.s + 32 * cut, &ntx, &nil, 1, in);
+        if (e == hipSuccess) e = c->eng.insert(in, 1, out);
+        if (e != hipSuccess) return dev_err(err, e, "hgx_insert_event_bodies");
+        if (out.code == hgx::INS_OK) c->eng.ids_known = false;   // (unreachable: the event was stored without an id)
+        out.accepted += ok_before;
+    }
+    return finish_insert(c, out, n_inserted, err);
 }
 
 // Core.Sync's loop (node/core.go:199-211) over a SyncResponse's WireEvents: ReadWireInfo

@@ -120,6 +120,7 @@ hipError_t Engine::share_round_rows(int32_t r_a, int32_t r_b) {
 }
 
 Engine::~Engine() {
+    free_ev_scratch(ev_scratch);
     if (pay_thread.joinable()) pay_thread.join();
     if (stream2) (void)hipStreamSynchronize(stream2);
     if (ev_pay) (void)hipEventDestroy(ev_pay);

@@ -93,6 +93,9 @@ struct InsertOut {
 };
 
 class Engine;
+struct BodiesIn;     // hgx_bodies.h
+struct EvScratch;    // hgx_goenc_dev.hip: the event-body front end's chunk buffers
+void free_ev_scratch(EvScratch* p);
 
 // A chain-sharded group (hgx_create_sharded / hgx_set_round_shards): W engines in one
 // process, shard k's on device dev[k] (devices may repeat), each holding the whole DAG. Shard k
@@ -135,6 +138,13 @@ class Engine {
                                InsertOut& out);
     hipError_t stage_sig(const uint8_t* digest, const uint8_t* r, int64_t count, const uint8_t** d_digest,
                          const uint8_t** d_r);
+    // the same with Event.Hash and Event.Verify's digest computed here from the events' fields (host
+    // columns): Go-JSON texts, ids in dependency order, body digests, then insert_verified, in internal
+    // chunks (hgx_goenc_dev.hip). txi: bodies_check's. out_id32 (host, may be null)
+    // gets the accepted prefix's ids.
+    hipError_t insert_bodies(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count, uint8_t* out_id32,
+                             InsertOut& out);
+    EvScratch* ev_scratch = nullptr;
     // participants' public keys (65 bytes each, C of them): device window tables built once
     hipError_t set_keys(const uint8_t* keys65);
     bool keys_set = false;

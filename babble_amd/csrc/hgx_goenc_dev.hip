@@ -1,0 +1,629 @@
+// Event bodies on the device: the Go-JSON of every event of a batch
+// (Event.Marshal, hashgraph/event.go:155-162: json.Encoder output of {Body, R, S}), the event ids
+// (Event.Hash :171-180 = SHA-256 of that text) in dependency order, the body digests
+// (EventBody.Hash :48-54 = SHA-256 of EventBody.Marshal, the bytes Event.Verify checks :142-152),
+// and the hand-over to the verified insert. The text of one event is
+//   {"Body":{"Transactions":T,"Parents":["SP","OP"],"Creator":"B64","Timestamp":"TS","Index":N},"R":DEC,"S":DEC}\n
+// (SURVEY Appendix B): T = null | [] | ["b64",...] (std base64 with padding), a parent = 0x + 64
+// upper-case hex digits or empty, Creator = base64 of the 65 key bytes, TS = RFC3339Nano in UTC,
+// N a signed decimal, R and S bare decimals. EventBody.Marshal is the {...} after "Body": plus '\n',
+// so the body digest is hashed out of the event's text with a one-byte suffix.
+//
+// One lane per event: a sizing pass (the same encoder into a counting sink), an exclusive scan, a
+// write pass that leaves the two parent slots open; then the id pass, one workgroup per graph looping
+// over the batch's dependency levels (a level's events patch their parents' hex into their text and
+// hash it; __syncthreads() and an agent-scope fence order the levels; no workgroup waits for
+// another); then the body digests, one lane per event.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "hgx.h"
+#include "hgx_bodies.h"
+#include "hgx_engine.h"
+#include "hgx_sha256_dev.h"
+
+#define HGX_TRY(x)                              \
+    do {                                        \
+        hipError_t _e = (x);                    \
+        if (_e != hipSuccess) return _e;        \
+    } while (0)
+
+namespace hgx {
+
+// ---- sinks: the encoder writes through one of these (host-callable as well: the text is plain
+// integer code, so a host harness can compare it with the oracle's encoder byte for byte) --------
+struct CountSink {
+    int64_t n = 0;
+    __host__ __device__ __forceinline__ void put(uint32_t) { n++; }
+    __host__ __device__ __forceinline__ void skip(int k) { n += k; }
+    __host__ __device__ __forceinline__ void finish() {}
+};
+
+// bytes gathered into aligned 4-byte stores; the first and last word of a run are stored bytewise
+struct ByteSink {
+    uint8_t* w;     // the aligned word being filled
+    uint32_t acc = 0;
+    int lo, nb;     // its bytes [lo, nb) are gathered in acc
+    int64_t n = 0;
+    __host__ __device__ __forceinline__ explicit ByteSink(uint8_t* p) {
+        lo = nb = (int)((uintptr_t)p & 3);
+        w = p - lo;
+    }
+    __host__ __device__ __forceinline__ void flush() {
+        if (lo == 0 && nb == 4) *(uint32_t*)w = acc;
+        else for (int j = lo; j < nb; j++) w[j] = (uint8_t)(acc >> (8 * j));
+        w += 4;
+        acc = 0;
+        lo = nb = 0;
+    }
+    __host__ __device__ __forceinline__ void put(uint32_t c) {
+        acc |= c << (8 * nb);
+        n++;
+        if (++nb == 4) flush();
+    }
+    __host__ __device__ __forceinline__ void skip(int k) {   // leave k bytes unwritten
+        uint8_t* p = w + nb + k;
+        if (nb > lo) flush();
+        lo = nb = (int)((uintptr_t)p & 3);
+        w = p - lo;
+        acc = 0;
+        n += k;
+    }
+    __host__ __device__ __forceinline__ void finish() {
+        if (nb > lo) flush();
+    }
+};
+
+template <typename S>
+__host__ __device__ __forceinline__ void put_str(S& s, const char* lit) {
+    for (; *lit; lit++) s.put((uint32_t)(uint8_t)*lit);
+}
+
+__host__ __device__ __forceinline__ uint32_t b64_char(uint32_t v) {
+    return v < 26 ? 'A' + v : v < 52 ? 'a' + (v - 26) : v < 62 ? '0' + (v - 52) : v == 62 ? '+' : '/';
+}
+
+template <typename S>
+__host__ __device__ __forceinline__ void put_base64(S& s, const uint8_t* in, int64_t len) {
+    int64_t i = 0;
+    for (; i + 3 <= len; i += 3) {
+        const uint32_t v = ((uint32_t)in[i] << 16) | ((uint32_t)in[i + 1] << 8) | in[i + 2];
+        s.put(b64_char(v >> 18)); s.put(b64_char((v >> 12) & 63)); s.put(b64_char((v >> 6) & 63)); s.put(b64_char(v & 63));
+    }
+    if (len - i == 1) {
+        const uint32_t v = (uint32_t)in[i] << 16;
+        s.put(b64_char(v >> 18)); s.put(b64_char((v >> 12) & 63)); s.put('='); s.put('=');
+    } else if (len - i == 2) {
+        const uint32_t v = ((uint32_t)in[i] << 16) | ((uint32_t)in[i + 1] << 8);
+        s.put(b64_char(v >> 18)); s.put(b64_char((v >> 12) & 63)); s.put(b64_char((v >> 6) & 63)); s.put('=');
+    }
+}
+
+__host__ __device__ __forceinline__ uint32_t hex_char(uint32_t v) { return v < 10 ? '0' + v : 'A' + (v - 10); }
+
+// "0x%X" of a 32-byte id (Event.Hex, event.go:183-188), read as 8 words (ids are 4-byte aligned);
+// FRESH: the id may have been written by another wave of this launch, so the words are read past L1
+template <bool FRESH, typename S>
+__host__ __device__ __forceinline__ void put_hex_id(S& s, const uint8_t* id) {
+    s.put('0');
+    s.put('x');
+    uint32_t* p = (uint32_t*)id;
+    for (int j = 0; j < 8; j++) {
+        const uint32_t x = FRESH ? __hip_atomic_load(p + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : p[j];
+        for (int b = 0; b < 4; b++) {
+            const uint32_t v = (x >> (8 * b)) & 0xFF;
+            s.put(hex_char(v >> 4));
+            s.put(hex_char(v & 15));
+        }
+    }
+}
+
+// v < 10^9 as decimal digits: all nine when `started`, else from its first non-zero digit (nothing
+// for 0); `keep` digits at most (the timestamp's fraction drops its trailing zeros)
+template <typename S>
+__host__ __device__ __forceinline__ void put_chunk9(S& s, uint32_t v, bool& started, int keep = 9) {
+    uint32_t d = 100000000u;
+#pragma unroll
+    for (int j = 0; j < 9; j++) {
+        const uint32_t q = v / d;
+        v -= q * d;
+        if (q) started = true;
+        if (started && j < keep) s.put('0' + q);
+        d /= 10;
+    }
+}
+
+template <typename S>
+__host__ __device__ __forceinline__ void put_u64(S& s, uint64_t v) {
+    const uint32_t c0 = (uint32_t)(v % 1000000000ull);
+    const uint64_t t = v / 1000000000ull;
+    const uint32_t c1 = (uint32_t)(t % 1000000000ull), c2 = (uint32_t)(t / 1000000000ull);
+    bool started = false;
+    put_chunk9(s, c2, started);
+    put_chunk9(s, c1, started);
+    put_chunk9(s, c0, started);
+    if (!started) s.put('0');
+}
+
+template <typename S>
+__host__ __device__ __forceinline__ void put_i64(S& s, int64_t v) {
+    if (v < 0) s.put('-');
+    put_u64(s, v < 0 ? 0 - (uint64_t)v : (uint64_t)v);
+}
+
+// big.Int.String of a 256-bit big-endian magnitude: eight 32-bit limbs divided by 10^9 nine times
+template <typename S>
+__host__ __device__ __forceinline__ void put_dec256(S& s, const uint8_t* be) {
+    uint32_t limb[8], chunk[9];
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+        limb[j] = ((uint32_t)be[4 * j] << 24) | ((uint32_t)be[4 * j + 1] << 16) | ((uint32_t)be[4 * j + 2] << 8) | be[4 * j + 3];
+#pragma unroll
+    for (int c = 0; c < 9; c++) {
+        uint64_t rem = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const uint64_t cur = (rem << 32) | limb[j];
+            limb[j] = (uint32_t)(cur / 1000000000ull);
+            rem = cur % 1000000000ull;
+        }
+        chunk[c] = (uint32_t)rem;
+    }
+    bool started = false;
+#pragma unroll
+    for (int c = 8; c >= 0; c--) put_chunk9(s, chunk[c], started);
+    if (!started) s.put('0');
+}
+
+template <typename S>
+__host__ __device__ __forceinline__ void put_2d(S& s, uint32_t v) {
+    s.put('0' + v / 10);
+    s.put('0' + v % 10);
+}
+
+// time.Time.MarshalJSON of a UTC instant (RFC3339Nano): floor division below 1970, the fraction
+// without its trailing zeros and absent when it is 0
+template <typename S>
+__host__ __device__ __forceinline__ void put_rfc3339nano(S& s, int64_t unix_ns) {
+    int64_t secs = unix_ns / 1000000000ll, nsec = unix_ns % 1000000000ll;
+    if (nsec < 0) { nsec += 1000000000ll; secs -= 1; }
+    int64_t days = secs / 86400, sod = secs % 86400;
+    if (sod < 0) { sod += 86400; days -= 1; }
+    // civil date of a day count (proleptic Gregorian)
+    const int64_t z = days + 719468;
+    const int64_t era = (z >= 0 ? z : z - 146096) / 146097;
+    const uint32_t doe = (uint32_t)(z - era * 146097);
+    const uint32_t yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365;
+    const uint32_t doy = doe - (365 * yoe + yoe / 4 - yoe / 100);
+    const uint32_t mp = (5 * doy + 2) / 153;
+    const uint32_t d = doy - (153 * mp + 2) / 5 + 1, m = mp < 10 ? mp + 3 : mp - 9;
+    const uint32_t y = (uint32_t)((int64_t)yoe + era * 400 + (m <= 2));   // 1677..2262 for an int64 of ns
+    put_2d(s, y / 100); put_2d(s, y % 100); s.put('-'); put_2d(s, m); s.put('-'); put_2d(s, d); s.put('T');
+    const uint32_t so = (uint32_t)sod;
+    put_2d(s, so / 3600); s.put(':'); put_2d(s, (so / 60) % 60); s.put(':'); put_2d(s, so % 60);
+    if (nsec) {
+        uint32_t f = (uint32_t)nsec;
+        int keep = 9;
+        while (f % 10 == 0) { f /= 10; keep--; }
+        s.put('.');
+        bool started = true;
+        put_chunk9(s, (uint32_t)nsec, started, keep);
+    }
+    s.put('Z');
+}
+
+// The event columns of one chunk on the device (one lane reads row k)
+struct EvCols {
+    const int32_t* creator;
+    const int64_t *index, *sp, *op, *ts;
+    const uint8_t *r, *s;
+    const int32_t* ntx;
+    const int64_t* txi;      // [m] the event's first entry of tx_off
+    const int64_t* tx_off;   // offsets into tx_bytes
+    const uint8_t* tx_bytes;
+    const uint8_t* keys65;   // [n_keys][65]
+    const uint8_t *sp_id, *op_id;   // [m][32] the parents' ids, or null: the slots stay open
+};
+
+// Event k's text into the sink; slot = where the self-parent string starts, body_end = one past the
+// body's closing brace (the body starts at byte 8)
+template <typename S>
+__host__ __device__ __forceinline__ void encode_event(S& s, const EvCols& c, int64_t k, int64_t& slot, int64_t& body_end) {
+    put_str(s, "{\"Body\":{\"Transactions\":");
+    const int ntx = c.ntx[k];
+    if (ntx < 0) {
+        put_str(s, "null");
+    } else {
+        s.put('[');
+        const int64_t t0 = c.txi[k];
+        for (int i = 0; i < ntx; i++) {
+            if (i) s.put(',');
+            s.put('"');
+            const int64_t a = c.tx_off[t0 + i];
+            put_base64(s, c.tx_bytes + a, c.tx_off[t0 + i + 1] - a);
+            s.put('"');
+        }
+        s.put(']');
+    }
+    put_str(s, ",\"Parents\":[\"");
+    slot = s.n;
+    if (c.sp[k] != -1) {
+        if (c.sp_id) put_hex_id<false>(s, c.sp_id + 32 * k);
+        else s.skip(66);
+    }
+    put_str(s, "\",\"");
+    if (c.op[k] != -1) {
+        if (c.op_id) put_hex_id<false>(s, c.op_id + 32 * k);
+        else s.skip(66);
+    }
+    put_str(s, "\"],\"Creator\":\"");
+    put_base64(s, c.keys65 + 65 * (int64_t)c.creator[k], 65);
+    put_str(s, "\",\"Timestamp\":\"");
+    put_rfc3339nano(s, c.ts[k]);
+    put_str(s, "\",\"Index\":");
+    put_i64(s, c.index[k]);
+    s.put('}');
+    body_end = s.n;
+    put_str(s, ",\"R\":");
+    put_dec256(s, c.r + 32 * k);
+    put_str(s, ",\"S\":");
+    put_dec256(s, c.s + 32 * k);
+    put_str(s, "}\n");
+    s.finish();
+}
+
+// ---- kernels ------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_ev_size(int64_t m, EvCols c, int64_t* __restrict__ len) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= m) return;
+    CountSink s;
+    int64_t slot, body_end;
+    encode_event(s, c, k, slot, body_end);
+    len[k] = s.n;
+}
+
+// off[0] = 0, off[k + 1] = off[k] + len[k] rounded up to `align` (a power of two): one workgroup,
+// every lane sums a contiguous run, the runs' sums are scanned in LDS
+__global__ void __launch_bounds__(1024) k_ev_scan(int64_t m, const int64_t* __restrict__ len, int64_t align,
+                                                  int64_t* __restrict__ off) {
+    __shared__ int64_t part[1024];
+    const int t = threadIdx.x;
+    const int64_t per = (m + 1023) / 1024, a = std::min(m, t * per), b = std::min(m, a + per);
+    int64_t sum = 0;
+    for (int64_t k = a; k < b; k++) sum += (len[k] + align - 1) & ~(align - 1);
+    part[t] = sum;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const int64_t v = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    int64_t run = part[t] - sum;
+    if (t == 0) off[0] = 0;
+    for (int64_t k = a; k < b; k++) {
+        run += (len[k] + align - 1) & ~(align - 1);
+        off[k + 1] = run;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_ev_write(int64_t m, EvCols c, const int64_t* __restrict__ off,
+                                                  uint8_t* __restrict__ text, int64_t* __restrict__ slot,
+                                                  int64_t* __restrict__ body_len) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= m) return;
+    ByteSink s(text + off[k]);
+    int64_t sl, body_end;
+    encode_event(s, c, k, sl, body_end);
+    if (slot) slot[k] = sl;
+    if (body_len) body_len[k] = body_end - 8;
+}
+
+// The id pass. Workgroup j owns one graph's events of the chunk, grouped by dependency level
+// (LevelPlan); level after level its lanes stride over the level's events: patch the parents' hex ids
+// into the open slots (a parent below `base` from the store's id column, a later one from this
+// chunk's ids), hash the text, store the id. A level's ids are complete before the next level reads
+// them: agent-scope fence, barrier, fence; the ids are read past L1. Every lane of the workgroup runs
+// the same wg_nl[j] rounds, and no workgroup waits for another.
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4)))
+k_ev_ids(const int32_t* __restrict__ wg_lo, const int32_t* __restrict__ wg_nl, const int32_t* __restrict__ loff,
+         const int32_t* __restrict__ pos, const int64_t* __restrict__ sp, const int64_t* __restrict__ op,
+         const int64_t* __restrict__ off, const int64_t* __restrict__ len, const int64_t* __restrict__ slot,
+         int64_t base, const uint8_t* store_id, uint8_t* text, uint8_t* ids) {
+    const int32_t lo = wg_lo[blockIdx.x], nl = wg_nl[blockIdx.x];
+    for (int32_t l = 0; l < nl; l++) {
+        const int32_t a = loff[lo + l], b = loff[lo + l + 1];
+        for (int32_t i = a + (int32_t)threadIdx.x; i < b; i += (int32_t)blockDim.x) {
+            const int64_t k = pos[i];
+            const int64_t o = off[k], s0 = sp[k], o0 = op[k];
+            int64_t at = o + slot[k];
+            if (s0 != -1) {
+                ByteSink w(text + at);
+                put_hex_id<true>(w, s0 < base ? store_id + 32 * s0 : ids + 32 * (s0 - base));
+                w.finish();
+                at += 66;
+            }
+            if (o0 != -1) {
+                ByteSink w(text + at + 3);
+                put_hex_id<true>(w, o0 < base ? store_id + 32 * o0 : ids + 32 * (o0 - base));
+                w.finish();
+            }
+            sha256_message<false>(text, o, len[k], 0, (uint32_t*)(ids + 32 * k));
+        }
+        __threadfence();
+        __syncthreads();
+        __threadfence();
+    }
+}
+
+// EventBody.Hash of every event: the body inside the event's text plus '\n'
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
+k_ev_digest(int64_t m, const uint8_t* __restrict__ text, const int64_t* __restrict__ off,
+            const int64_t* __restrict__ body_len, uint8_t* __restrict__ dig) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= m) return;
+    sha256_message<true>(text, off[k] + 8, body_len[k], '\n', (uint32_t*)(dig + 32 * k));
+}
+
+// ---- one chunk's buffers ------------------------------------------------------------------------
+namespace {
+
+struct DevMem {
+    uint8_t* p = nullptr;
+    size_t cap = 0;
+    hipError_t need(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        const hipError_t e = hipMalloc((void**)&p, bytes);
+        if (e == hipSuccess) cap = bytes;
+        return e;
+    }
+    ~DevMem() { if (p) (void)hipFree(p); }
+};
+
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+}  // namespace
+
+// The inputs of a chunk cross in one copy from a pinned blob; texts, lengths, ids and digests live in
+// buffers that grow to the largest chunk seen (bounded by the chunk limits of hgx_bodies.h).
+struct EvScratch {
+    DevMem in, text, meta, ids;
+    uint8_t* h = nullptr;
+    size_t h_cap = 0;
+    LevelPlan plan;
+    std::vector<int32_t> level;
+    ~EvScratch() { if (h) (void)hipHostFree(h); }
+
+    // device views of the staged chunk
+    EvCols cols{};
+    const int32_t *d_wg_lo = nullptr, *d_wg_nl = nullptr, *d_loff = nullptr, *d_pos = nullptr;
+    int64_t *d_len = nullptr, *d_off = nullptr, *d_slot = nullptr, *d_blen = nullptr;
+    uint8_t *d_ids = nullptr, *d_dig = nullptr;
+
+    // Stage events [lo, hi) (m of them): columns, transactions, the parents' ids (json mode) or the
+    // level plan (insert mode, base = gid of event lo) in ONE host-to-device copy.
+    hipError_t stage(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t lo, int64_t hi, const uint8_t* keys_dev,
+                     const uint8_t* keys_host, int32_t n_keys, const uint8_t* sp_id, const uint8_t* op_id, bool with_plan,
+                     int64_t base, int32_t n_per_graph, hipStream_t s) {
+        const size_t m = (size_t)(hi - lo);
+        const int64_t t0 = txi[(size_t)lo], t1 = txi[(size_t)hi];
+        const size_t nt = (size_t)(t1 - t0);
+        const int64_t b0 = ev.tx_off[t0];
+        const size_t nbytes = (size_t)(ev.tx_off[t1] - b0);
+        if (with_plan) {
+            level.resize(m);
+            int32_t nl = 0;
+            (void)batch_levels(ev.sp + lo, ev.op + lo, (int64_t)m, base, level.data(), &nl);
+            plan_levels(ev.creator + lo, level.data(), (int64_t)m, n_per_graph, plan);
+        }
+        const size_t nwg = with_plan ? plan.wg_lo.size() : 0, nloff = with_plan ? plan.loff.size() : 0;
+        const void* src[16] = {ev.creator + lo, ev.index + lo, ev.sp + lo, ev.op + lo, ev.ts + lo, ev.r + 32 * lo,
+                               ev.s + 32 * lo, ev.ntx + lo, nullptr, nullptr, nbytes ? ev.tx_bytes + b0 : nullptr,
+                               keys_host, sp_id ? sp_id + 32 * lo : nullptr, op_id ? op_id + 32 * lo : nullptr, nullptr,
+                               nullptr};
+        size_t bytes[18] = {4 * m, 8 * m, 8 * m, 8 * m, 8 * m, 32 * m, 32 * m, 4 * m, 8 * m, 8 * (nt + 1), nbytes,
+                            keys_host ? (size_t)65 * (size_t)n_keys : 0, sp_id ? 32 * m : 0, op_id ? 32 * m : 0,
+                            4 * nwg, 4 * nwg, 4 * nloff, with_plan ? 4 * m : 0};
+        size_t o[18], total = 0;
+        for (int i = 0; i < 18; i++) {
+            o[i] = total;
+            total += up256(bytes[i] + 16);   // (16 spare bytes: the hash reader's aligned loads)
+        }
+        if (h_cap < total) {
+            if (h) (void)hipHostFree(h);
+            h = nullptr;
+            h_cap = 0;
+            HGX_TRY(hipHostMalloc((void**)&h, total, hipHostMallocDefault));
+            h_cap = total;
+        }
+        HGX_TRY(in.need(total));
+        for (int i = 0; i < 14; i++)
+            if (src[i] && bytes[i]) std::memcpy(h + o[i], src[i], bytes[i]);
+        int64_t* h_txi = (int64_t*)(h + o[8]);
+        for (size_t k = 0; k < m; k++) h_txi[k] = txi[(size_t)lo + k] - t0;
+        int64_t* h_off = (int64_t*)(h + o[9]);
+        for (size_t j = 0; j <= nt; j++) h_off[j] = ev.tx_off[t0 + (int64_t)j] - b0;
+        if (with_plan) {
+            if (nwg) std::memcpy(h + o[14], plan.wg_lo.data(), 4 * nwg);
+            if (nwg) std::memcpy(h + o[15], plan.wg_nl.data(), 4 * nwg);
+            if (nloff) std::memcpy(h + o[16], plan.loff.data(), 4 * nloff);
+            std::memcpy(h + o[17], plan.pos.data(), 4 * m);
+        }
+        HGX_TRY(hipMemcpyAsync(in.p, h, total, hipMemcpyHostToDevice, s));
+        uint8_t* d = in.p;
+        cols.creator = (const int32_t*)(d + o[0]); cols.index = (const int64_t*)(d + o[1]);
+        cols.sp = (const int64_t*)(d + o[2]); cols.op = (const int64_t*)(d + o[3]); cols.ts = (const int64_t*)(d + o[4]);
+        cols.r = d + o[5]; cols.s = d + o[6]; cols.ntx = (const int32_t*)(d + o[7]);
+        cols.txi = (const int64_t*)(d + o[8]); cols.tx_off = (const int64_t*)(d + o[9]); cols.tx_bytes = d + o[10];
+        cols.keys65 = keys_host ? d + o[11] : keys_dev;
+        cols.sp_id = sp_id ? d + o[12] : nullptr; cols.op_id = op_id ? d + o[13] : nullptr;
+        d_wg_lo = (const int32_t*)(d + o[14]); d_wg_nl = (const int32_t*)(d + o[15]);
+        d_loff = (const int32_t*)(d + o[16]); d_pos = (const int32_t*)(d + o[17]);
+        // lengths, offsets (m + 1), slots, body lengths; ids and digests (16-byte aligned)
+        HGX_TRY(meta.need(up256(8 * m) * 3 + up256(8 * (m + 1))));
+        d_len = (int64_t*)meta.p; d_off = (int64_t*)(meta.p + up256(8 * m));
+        d_slot = (int64_t*)((uint8_t*)d_off + up256(8 * (m + 1))); d_blen = (int64_t*)((uint8_t*)d_slot + up256(8 * m));
+        HGX_TRY(ids.need(2 * up256(32 * m)));
+        d_ids = ids.p; d_dig = ids.p + up256(32 * m);
+        return hipSuccess;
+    }
+
+    hipError_t size_and_scan(int64_t m, int64_t align, hipStream_t s) {
+        const unsigned blocks = (unsigned)((m + 255) / 256);
+        hipLaunchKernelGGL(k_ev_size, dim3(blocks), dim3(256), 0, s, m, cols, d_len);
+        hipLaunchKernelGGL(k_ev_scan, dim3(1), dim3(1024), 0, s, m, (const int64_t*)d_len, align, d_off);
+        return hipGetLastError();
+    }
+
+    hipError_t write(int64_t m, size_t text_bytes, bool with_meta, hipStream_t s) {
+        HGX_TRY(text.need(text_bytes + 64));
+        const unsigned blocks = (unsigned)((m + 255) / 256);
+        hipLaunchKernelGGL(k_ev_write, dim3(blocks), dim3(256), 0, s, m, cols, (const int64_t*)d_off, text.p,
+                           with_meta ? d_slot : nullptr, with_meta ? d_blen : nullptr);
+        return hipGetLastError();
+    }
+};
+
+void free_ev_scratch(EvScratch* p) { delete p; }
+
+// InsertEvent with Event.Hash and Event.Verify computed here (hgx_insert_event_bodies): chunk after
+// chunk, texts -> ids in level order -> body digests -> insert_verified with the chunk's id buffer
+// as the hash column. Stops at the first chunk with a rejected event; out is the last insert's with
+// accepted = the whole call's. Every event of [0, count) has a text (the caller cut the batch).
+hipError_t Engine::insert_bodies(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count, uint8_t* out_id32,
+                                 InsertOut& out) {
+    if (!ev_scratch) ev_scratch = new EvScratch();
+    EvScratch& sc = *ev_scratch;
+    int64_t done = 0;
+    out = InsertOut();
+    if (count <= 0) return insert_verified(InsertIn{}, nullptr, nullptr, 0, out);
+    while (done < count) {
+        int64_t bound = 0;
+        const int64_t hi = bodies_chunk_end(ev, txi, done, count, &bound);
+        const int64_t m = hi - done;
+        HGX_TRY(sc.stage(ev, txi, done, hi, pk_keys.p, nullptr, C, nullptr, nullptr, true, E, n, stream));
+        HGX_TRY(sc.size_and_scan(m, 16, stream));
+        HGX_TRY(sc.write(m, (size_t)bound, true, stream));
+        const int bs = std::min(1024, std::max(64, (sc.plan.max_width + 63) & ~63));
+        hipLaunchKernelGGL(k_ev_ids, dim3((unsigned)sc.plan.wg_lo.size()), dim3(bs), 0, stream, sc.d_wg_lo, sc.d_wg_nl,
+                           sc.d_loff, sc.d_pos, sc.cols.sp, sc.cols.op, (const int64_t*)sc.d_off, (const int64_t*)sc.d_len,
+                           (const int64_t*)sc.d_slot, E, (const uint8_t*)g_id.p, sc.text.p, sc.d_ids);
+        hipLaunchKernelGGL(k_ev_digest, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, m,
+                           (const uint8_t*)sc.text.p, (const int64_t*)sc.d_off, (const int64_t*)sc.d_blen, sc.d_dig);
+        HGX_TRY(hipGetLastError());
+        InsertIn in{};
+        in.creator = sc.cols.creator; in.index = sc.cols.index; in.sp = sc.cols.sp; in.op = sc.cols.op;
+        in.ts = sc.cols.ts; in.hash = sc.d_ids; in.S = sc.cols.s; in.ntx = sc.cols.ntx; in.nil = nullptr;
+        InsertOut co;
+        HGX_TRY(insert_verified(in, sc.d_dig, sc.cols.r, m, co));
+        if (out_id32 && co.accepted > 0) {
+            HGX_TRY(hipMemcpyAsync(out_id32 + 32 * done, sc.d_ids, 32 * (size_t)co.accepted, hipMemcpyDeviceToHost, stream));
+            HGX_TRY(hipStreamSynchronize(stream));
+        }
+        done += co.accepted;
+        const int64_t total = done;
+        out = std::move(co);
+        out.accepted = total;
+        if (out.code) break;
+    }
+    return hipSuccess;
+}
+
+}  // namespace hgx
+
+// ---- the encoder alone ----------------------------------------------------------------------
+namespace {
+
+void set_err(hgx_error* err, int32_t code, const char* msg) {
+    if (!err) return;
+    err->code = code;
+    std::snprintf(err->msg, sizeof(err->msg), "%s", msg);
+}
+
+int32_t invalid(hgx_error* err, const char* msg) {
+    set_err(err, HGX_ERR_INVALID, msg);
+    return HGX_ERR_INVALID;
+}
+
+}  // namespace
+
+extern "C" int32_t hgx_event_json_batch(int32_t device, const hgx_event_bodies* evb, int64_t count, const uint8_t* keys65,
+                                        int32_t n_keys, const uint8_t* sp_id32, const uint8_t* op_id32, uint8_t* out,
+                                        int64_t out_cap, int64_t* offsets, hgx_error* err) {
+    set_err(err, HGX_OK, "");
+    if (!evb || count < 0 || !offsets || n_keys < 0 || (count > 0 && (!keys65 || !sp_id32 || !op_id32)) ||
+        (out && out_cap < 0))
+        return invalid(err, "hgx_event_json_batch: bad arguments");
+    const hgx::BodiesIn ev{evb->creator, evb->index, evb->self_parent, evb->other_parent, evb->timestamp_ns,
+                           evb->sig_r, evb->sig_s, evb->ntx, evb->tx_off, evb->tx_bytes};
+    std::vector<int64_t> txi;
+    if (const char* why = hgx::bodies_check(ev, count, txi)) {
+        char msg[128];
+        std::snprintf(msg, sizeof(msg), "hgx_event_json_batch: %s", why);
+        return invalid(err, msg);
+    }
+    for (int64_t k = 0; k < count; k++)
+        if (ev.creator[k] < 0 || ev.creator[k] >= n_keys) return invalid(err, "hgx_event_json_batch: creator without a key");
+    offsets[0] = 0;
+    if (count == 0) return HGX_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        set_err(err, HGX_ERR_DEVICE, "no HIP device available (libhgx has no CPU fallback)");
+        return HGX_ERR_DEVICE;
+    }
+    hipDeviceProp_t prop;
+    if (device < 0 || device >= ndev || hipGetDeviceProperties(&prop, device) != hipSuccess ||
+        std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+        set_err(err, HGX_ERR_DEVICE, "libhgx is built for gfx950 (MI355X) only");
+        return HGX_ERR_DEVICE;
+    }
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    (void)hipSetDevice(device);
+    hipStream_t s = nullptr;
+    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    bool fits = true;
+    {
+        hgx::EvScratch sc;
+        int64_t done = 0, at = 0;
+        while (e == hipSuccess && done < count) {
+            int64_t bound = 0;
+            const int64_t hi = hgx::bodies_chunk_end(ev, txi, done, count, &bound);
+            const int64_t m = hi - done;
+            e = sc.stage(ev, txi, done, hi, nullptr, keys65, n_keys, sp_id32, op_id32, false, 0, 1, s);
+            if (e == hipSuccess) e = sc.size_and_scan(m, 1, s);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(offsets + done + 1, sc.d_off + 1, 8 * (size_t)m, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess) break;
+            const int64_t bytes = offsets[hi];   // (chunk-relative until rebased below)
+            for (int64_t k = done + 1; k <= hi; k++) offsets[k] += at;
+            if (out && fits && at + bytes <= out_cap) {
+                e = sc.write(m, (size_t)bytes, false, s);
+                if (e == hipSuccess && bytes)
+                    e = hipMemcpyAsync(out + at, sc.text.p, (size_t)bytes, hipMemcpyDeviceToHost, s);
+                if (e == hipSuccess) e = hipStreamSynchronize(s);
+            } else if (out) {
+                fits = false;
+            }
+            at += bytes;
+            done = hi;
+        }
+    }
+    if (s) (void)hipStreamDestroy(s);
+    (void)hipSetDevice(prev);
+    if (e != hipSuccess) {
+        set_err(err, HGX_ERR_DEVICE, hipGetErrorString(e));
+        return HGX_ERR_DEVICE;
+    }
+    if (!fits) return invalid(err, "hgx_event_json_batch: out_cap is smaller than the batch's text");
+    return HGX_OK;
+}

@@ -104,6 +104,77 @@ def _events32_of(cols: dict, lo: int, hi: int):
     return a, _lib.hgx_events32(*[ptr(a[k]) for k in ("creator", "index", "sp", "op", "ts", "coin", "s", "ntx")])
 
 
+def body_columns(creator, index, sp, op, ts, r, s, txs) -> dict:
+    """hgx_event_bodies columns (include/hgx.h) of a batch: the DAG fields, the signatures' R and S
+    (32 bytes big-endian each) and txs[k] = Body.Transactions of event k (None for nil, else a list of
+    byte strings)."""
+    ntx = np.fromiter((-1 if t is None else len(t) for t in txs), np.int32, count=len(txs))
+    flat = [b for t in txs if t for b in t]
+    tx_off = np.zeros(len(flat) + 1, np.int64)
+    np.cumsum(np.fromiter((len(b) for b in flat), np.int64, count=len(flat)), out=tx_off[1:])
+    return dict(creator=np.ascontiguousarray(creator, np.int32), index=np.ascontiguousarray(index, np.int64),
+                sp=np.ascontiguousarray(sp, np.int64), op=np.ascontiguousarray(op, np.int64),
+                ts=np.ascontiguousarray(ts, np.int64), r=np.ascontiguousarray(r, np.uint8).reshape(-1, 32),
+                s=np.ascontiguousarray(s, np.uint8).reshape(-1, 32), ntx=ntx, tx_off=tx_off,
+                tx_bytes=np.frombuffer(b"".join(flat) + b"\0", np.uint8))
+
+
+def _event_bodies_of(cols: dict, lo: int, hi: int):
+    """The hgx_event_bodies of events [lo, hi) (tx_off starts at the slice's first transaction)."""
+    a = {k: np.ascontiguousarray(cols[k][lo:hi]) for k in ("creator", "index", "sp", "op", "ts", "r", "s", "ntx")}
+    first = int(np.maximum(cols["ntx"][:lo], 0).sum())
+    a["tx_off"] = np.ascontiguousarray(cols["tx_off"][first:])
+    a["tx_bytes"] = cols["tx_bytes"]
+    return a, _lib.hgx_event_bodies(*[ptr(a[k]) for k in ("creator", "index", "sp", "op", "ts", "r", "s", "ntx",
+                                                          "tx_off", "tx_bytes")])
+
+
+def event_json_batch(cols: dict, keys65, sp_id32, op_id32, device: int = 0, out_cap: Optional[int] = None):
+    """Event.Marshal bytes of body_columns() events whose parents' ids the caller supplies
+    (hgx_event_json_batch). Returns (data, offsets): event k's text is data[offsets[k]:offsets[k+1]].
+    out_cap = 0 sizes only (data is empty); a smaller out_cap than the text needs raises HgxError with
+    .offsets filled."""
+    L = _lib.lib()
+    m = len(cols["creator"])
+    _, ev = _event_bodies_of(cols, 0, m)
+    keys = np.ascontiguousarray(keys65, np.uint8).reshape(-1, 65)
+    spi = np.ascontiguousarray(sp_id32, np.uint8).reshape(-1, 32)
+    opi = np.ascontiguousarray(op_id32, np.uint8).reshape(-1, 32)
+    offsets = np.zeros(m + 1, np.int64)
+
+    def call(out, cap):
+        err = hgx_error()
+        rc = L.hgx_event_json_batch(device, C.byref(ev), m, ptr(keys), len(keys), ptr(spi), ptr(opi),
+                                    ptr(out) if out is not None else None, cap, ptr(offsets), C.byref(err))
+        if rc:
+            e = HgxError(int(err.code or rc), err.msg.decode(errors="replace"))
+            e.offsets = offsets
+            raise e
+
+    if out_cap is None:
+        call(None, 0)
+        out_cap = int(offsets[m])
+    elif out_cap == 0:
+        call(None, 0)
+        return np.zeros(0, np.uint8), offsets
+    out = np.zeros(max(out_cap, 1), np.uint8)
+    call(out, out_cap)
+    return out[:int(offsets[m])], offsets
+
+
+def batch_levels(sp, op, base: int = 0):
+    """Each event's depth inside a batch whose first event gets gid `base` (hgx_batch_levels, host
+    only): returns (level [count] int32, number of levels)."""
+    sp = np.ascontiguousarray(sp, np.int64)
+    op = np.ascontiguousarray(op, np.int64)
+    level = np.zeros(len(sp), np.int32)
+    nl = C.c_int32(0)
+    err = hgx_error()
+    rc = _lib.lib().hgx_batch_levels(ptr(sp), ptr(op), len(sp), base, ptr(level), C.byref(nl), C.byref(err))
+    _lib.check(rc, err)
+    return level, nl.value
+
+
 class Hashgraph:
     """One context = NewHashgraph(participants, NewInmemStore(participants, cap)) (hashgraph.go:39-66).
 
@@ -187,6 +258,24 @@ class Hashgraph:
             e.inserted = n_ins.value
             raise e
         return n_ins.value
+
+    def insert_bodies(self, cols: dict, lo: int = 0, hi: Optional[int] = None) -> np.ndarray:
+        """InsertEvent with Event.Hash and Event.Verify computed on the device from the events' fields
+        (hgx_insert_event_bodies): events [lo, hi) of body_columns(). Returns the events' ids
+        [(hi - lo), 32]. Raises HgxError on the first rejected event, with .inserted = events inserted
+        before it and .ids = their ids."""
+        hi = len(cols["creator"]) if hi is None else hi
+        a, ev = _event_bodies_of(cols, lo, hi)
+        ids = np.zeros((hi - lo, 32), np.uint8)
+        err = hgx_error()
+        n_ins = C.c_int64(0)
+        rc = self.L.hgx_insert_event_bodies(self.ctx, C.byref(ev), hi - lo, ptr(ids), C.byref(n_ins), C.byref(err))
+        if rc:
+            e = HgxError(int(err.code or rc), err.msg.decode(errors="replace"))
+            e.inserted = n_ins.value
+            e.ids = ids[:n_ins.value]
+            raise e
+        return ids
 
     def insert_verified_device(self, dt: "DeviceTrace", d_digest, d_r, lo: int = 0, hi: Optional[int] = None) -> int:
         """The same with every column resident in HBM (d_digest / d_r: device addresses of 32-byte rows)."""

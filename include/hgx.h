@@ -36,7 +36,9 @@
 extern "C" {
 #endif
 
-#define HGX_ABI_VERSION 6   /* 6: hgx_host_alloc / hgx_host_free (page-locked caller buffers);
+#define HGX_ABI_VERSION 6   /* (still 6 with hgx_insert_event_bodies, hgx_event_json_batch and hgx_batch_levels:
+                                 purely additive, no existing entry or structure changed)
+                              6: hgx_host_alloc / hgx_host_free (page-locked caller buffers);
                               5: hgx_events_packed (hgx_insert_events_packed, hgx_insert_and_run_packed,
                                  hgx_pack_events32);
                               4: hgx_create_sharded (chain-sharded recurrence over devices);
@@ -206,6 +208,63 @@ int32_t hgx_insert_events_verified(hgx_ctx* ctx, const hgx_events* ev, const uin
                                    int64_t count, int64_t* n_inserted, hgx_error* err);
 int32_t hgx_insert_events_verified_device(hgx_ctx* ctx, const hgx_events* ev, const uint8_t* digest32,
                                           const uint8_t* sig_r32, int64_t count, int64_t* n_inserted, hgx_error* err);
+/* Event fields instead of event hashes (hashgraph/event.go:14-37): what a node holds after decoding
+ * a sync batch, before any hashing. */
+typedef struct {
+    const int32_t* creator;       /* participant id; Body.Creator = that participant's 65-byte key */
+    const int64_t* index;         /* Body.Index */
+    const int64_t* self_parent;   /* gid, -1 for "" */
+    const int64_t* other_parent;  /* gid, -1 for "" */
+    const int64_t* timestamp_ns;  /* Body.Timestamp as Unix ns (UTC) */
+    const uint8_t* sig_r;         /* 32 B big-endian each */
+    const uint8_t* sig_s;
+    const int32_t* ntx;           /* len(Body.Transactions), -1 for nil */
+    const int64_t* tx_off;        /* T+1 byte offsets into tx_bytes, T = sum(max(ntx,0)); an event's
+                                     transactions are consecutive entries, events in batch order */
+    const uint8_t* tx_bytes;
+} hgx_event_bodies;
+/* InsertEvent including Event.Hash and Event.Verify (hashgraph.go:356-363, event.go:142-188), host
+ * pointers: the device builds every event's Go-JSON (Event.Marshal), computes the event ids (SHA-256
+ * of that text) level by level -- an event's text holds its parents' hex ids, so a batch is hashed in
+ * dependency order (hgx_batch_levels) --, the body digests (EventBody.Hash), and hands both to the
+ * verified insert. A parent's id comes from the store's id column for a gid below hgx_num_events and
+ * from this batch for a later gid. Results, error strings, stop-at-first-failure and *n_inserted are
+ * those of hgx_insert_events_verified on the same events with host-computed hash and digest32;
+ * out_id32 (may be NULL) receives the ids of the accepted prefix, 32 bytes each, and
+ * hgx_get_event_id works afterwards. Needs hgx_set_participant_keys. HGX_ERR_INVALID "<reason>":
+ * bad columns (a NULL column, ntx < -1, decreasing tx_off: checked before anything else), keys not
+ * set, the context's ids are not known (events came through hgx_events32 / packed inserts or an
+ * id-less bootstrap), the context is in use after hgx_reset, or it is chain-sharded or row-sharded.
+ * Deviation from the reference: an event whose creator has no key, or with a parent that is neither
+ * -1 nor an earlier gid (HGX_UNKNOWN_PARENT included), has no id string, so no text. The batch is
+ * cut before it, the prefix is inserted first (its first failure wins), then the event fails with
+ * its parent check's Go error (CheckSelfParent / CheckOtherParent / "<creator>, Not Found") and
+ * *n_inserted = its position; the reference would report "Invalid signature" first when its
+ * signature is bad as well.
+ * Scratch: the batch is processed in internal chunks of at most 65 536 events and 32 MiB of JSON
+ * (8 bytes counted per transaction on top of its base64), so the scratch the context keeps is bounded
+ * whatever the batch size: on the device 32 MiB of text, at most 24 MiB of transaction bytes and 32 MiB
+ * of their offsets, and 220 bytes per event of a chunk for columns, level plan, ids and digests (under
+ * 104 MiB in all); the same without the text in page-locked host memory. Only a single event whose
+ * own text exceeds 32 MiB raises it, to that event's size. */
+int32_t hgx_insert_event_bodies(hgx_ctx* ctx, const hgx_event_bodies* ev, int64_t count, uint8_t* out_id32,
+                                int64_t* n_inserted, hgx_error* err);
+/* The encoder alone: Event.Marshal bytes (json.Encoder output of {Body, R, S}, event.go:155-162) of
+ * a batch whose parents' ids the caller supplies (sp_id32 / op_id32: 32 bytes per event, ignored
+ * where the parent gid is -1; a parent is printed when its gid is not -1). keys65: n_keys keys of 65
+ * bytes, creator[k] in [0, n_keys). Event k's text is out[offsets[k], offsets[k+1]); offsets gets
+ * count + 1 entries. out == NULL sizes only; with out_cap smaller than offsets[count] the call
+ * returns HGX_ERR_INVALID and still fills offsets. EventBody.Marshal is the text from byte 8 up to
+ * and including the '}' before ,"R": followed by '\n'. Host pointers. */
+int32_t hgx_event_json_batch(int32_t device, const hgx_event_bodies* ev, int64_t count, const uint8_t* keys65,
+                             int32_t n_keys, const uint8_t* sp_id32, const uint8_t* op_id32, uint8_t* out,
+                             int64_t out_cap, int64_t* offsets, hgx_error* err);
+/* Host helper (no device): each event's depth inside a batch whose first event gets gid `base`:
+ * level[k] = 0 when no parent has gid >= base, else 1 + the maximum over its in-batch parents;
+ * *n_levels = the largest level + 1 (0 for an empty batch). Events of one level do not depend on
+ * each other. HGX_ERR_INVALID for a parent gid >= the event's own gid (base + k). */
+int32_t hgx_batch_levels(const int64_t* self_parent, const int64_t* other_parent, int64_t count, int64_t base,
+                         int32_t* level, int32_t* n_levels, hgx_error* err);
 /* WireEvents (event.go:252-267) as a SyncResponse carries them (net/commands.go:10-15), the
  * caller having decoded the JSON: the participants' ids instead of hashes. */
 typedef struct {
