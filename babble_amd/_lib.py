@@ -202,6 +202,9 @@ def lib():
     _sig(L, "hgx_insert_wire_events", i32, [p, p, i64, p, p])
     _sig(L, "hgx_set_commit_callback", i32, [p, C.c_void_p, p])
     _sig(L, "hgx_get_frame", i32, [p, p, i64, p, p, p, p, p, p, p, i64, p, p])
+    _sig(L, "hgx_prune_to_frame", i32, [p, p, i64, C.POINTER(C.c_int64), E])
+    _sig(L, "hgx_get_root_ids", i32, [p, i32, p, C.POINTER(C.c_int32), p, C.POINTER(C.c_int32), E])
+    _sig(L, "hgx_get_root_others", i32, [p, p, p, i64, C.POINTER(C.c_int64), E])
     _sig(L, "hgx_shard_values", i64, [p, i32])
     _sig(L, "hgx_shard_export", i32, [p, p, i32])
     _sig(L, "hgx_shard_import", i32, [p, i32, p, i32])

@@ -6,6 +6,7 @@
 // quirk, per-witness fame frozen once decided, LastConsensusRound /
 // LastCommitedRoundEvents, received events, blocks, counters.
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -142,6 +143,12 @@ struct hgx_ctx {
     };
     std::vector<Kept> reset_kept;
     std::vector<uint8_t> others_keys;            // Root.Others keys (hgx_set_root_others), 32 bytes each
+    // the roots' ids (hgx_get_root_ids / hgx_get_root_others): known while every root traces back to
+    // genesis through hgx_prune_to_frame, which gathers them before the dropped events go
+    bool root_ids_known = true;
+    std::vector<uint8_t> root_x_id, root_y_id;     // [C][32]
+    std::vector<uint8_t> root_has_x, root_has_y;   // [C] 0: "" (a genesis root's X / Y)
+    std::vector<std::array<uint8_t, 64>> root_others;   // (event id, other-parent id), sorted
     std::vector<int64_t> pl_off;                 // per-event payloads restored by hgx_bootstrap ([E0, E0 + m))
     std::vector<uint8_t> pl_blob;
     // commitCh (hashgraph.go:848-854): called for every new block with transactions
@@ -309,6 +316,10 @@ static hgx_ctx* create_batch_impl(int32_t n_graphs, int32_t n_participants, int6
     c->root_index.assign(c->C, -1);   // NewBaseRoot (root.go:69-76)
     c->root_round.assign(c->C, -1);
     c->root_y_ext.assign(c->C, 0);
+    c->root_x_id.assign((size_t)c->C * 32, 0);
+    c->root_y_id.assign((size_t)c->C * 32, 0);
+    c->root_has_x.assign(c->C, 0);
+    c->root_has_y.assign(c->C, 0);
     c->gs.assign(n_graphs, GraphState());
     c->order = std::vector<GraphOrder>(n_graphs);
     c->g_events.assign(n_graphs, 0);
@@ -1036,6 +1047,10 @@ static int32_t clear_one(hgx_ctx* c) {
     c->pl_blob.clear();
     c->reset_kept.clear();
     c->others_keys.clear();
+    c->root_ids_known = true;
+    std::fill(c->root_has_x.begin(), c->root_has_x.end(), 0);
+    std::fill(c->root_has_y.begin(), c->root_has_y.end(), 0);
+    c->root_others.clear();
     if (c->rooted) {   // a fresh NewHashgraph has genesis roots
         std::fill(c->root_index.begin(), c->root_index.end(), -1);
         std::fill(c->root_round.begin(), c->root_round.end(), -1);
@@ -1387,33 +1402,9 @@ int32_t hgx_get_event_payload(hgx_ctx* c, int64_t gid, uint8_t* out, int64_t cap
     return ok(err);
 }
 
-// ---- Reset (hashgraph.go:877-895, inmem_store.go:184-192) ---------------------------------
-// Store.Reset: new roots, the event / round / consensus caches and the participants'
-// RollingIndexes cleared, lastRound = -1 (the block cache is kept). Hashgraph.Reset:
-// UndeterminedEvents, UndecidedRounds (empty), PendingLoadedEvents, topologicalIndex and the
-// memo caches; LastConsensusRound, LastCommitedRoundEvents and ConsensusTransactions are kept.
-int32_t hgx_reset(hgx_ctx* c, const int32_t* root_index, const int32_t* root_round, const int32_t* root_y_is_event,
-                  hgx_error* err) {
-    if (!c || !root_index || !root_round || !root_y_is_event) {
-        set_err(err, HGX_ERR_INVALID, "hgx_reset: bad arguments");
-        return HGX_ERR_INVALID;
-    }
-    if (group_only_one(c, err, "hgx_reset")) return HGX_ERR_INVALID;
-    DeviceGuard dg(c);
-    std::vector<int32_t> rr(root_round, root_round + c->C);
-    std::vector<uint8_t> ye(c->C);
-    bool rooted = false;
-    for (int p = 0; p < c->C; p++) {
-        ye[p] = root_y_is_event[p] ? 1 : 0;
-        if (rr[p] >= 0 || ye[p]) rooted = true;
-    }
-    if (rooted && c->G != 1) {
-        set_err(err, HGX_ERR_INVALID, "hgx_reset: roots need a single-graph context");
-        return HGX_ERR_INVALID;
-    }
-    if (c->eng.clear() != hipSuccess || c->eng.set_roots(rr, ye) != hipSuccess ||
-        c->eng.set_root_others(nullptr, 0) != hipSuccess)
-        return dev_err(err, hipErrorUnknown, "hgx_reset");
+// the host half of Reset: the new roots, what Reset keeps (as it is now) and a store without events
+static void reset_host_state(hgx_ctx* c, const int32_t* root_index, const std::vector<int32_t>& rr,
+                             const std::vector<uint8_t>& ye, bool rooted) {
     c->root_index.assign(root_index, root_index + c->C);
     c->root_round = rr;
     c->root_y_ext = ye;
@@ -1456,6 +1447,40 @@ int32_t hgx_reset(hgx_ctx* c, const int32_t* root_index, const int32_t* root_rou
     c->fo_prev_valid = false;
     c->mirror_ok = c->chains_ok = false;
     c->rounds_cached = c->recv_cached = false;
+}
+
+// ---- Reset (hashgraph.go:877-895, inmem_store.go:184-192) ---------------------------------
+// Store.Reset: new roots, the event / round / consensus caches and the participants'
+// RollingIndexes cleared, lastRound = -1 (the block cache is kept). Hashgraph.Reset:
+// UndeterminedEvents, UndecidedRounds (empty), PendingLoadedEvents, topologicalIndex and the
+// memo caches; LastConsensusRound, LastCommitedRoundEvents and ConsensusTransactions are kept.
+int32_t hgx_reset(hgx_ctx* c, const int32_t* root_index, const int32_t* root_round, const int32_t* root_y_is_event,
+                  hgx_error* err) {
+    if (!c || !root_index || !root_round || !root_y_is_event) {
+        set_err(err, HGX_ERR_INVALID, "hgx_reset: bad arguments");
+        return HGX_ERR_INVALID;
+    }
+    if (group_only_one(c, err, "hgx_reset")) return HGX_ERR_INVALID;
+    DeviceGuard dg(c);
+    std::vector<int32_t> rr(root_round, root_round + c->C);
+    std::vector<uint8_t> ye(c->C);
+    bool rooted = false;
+    for (int p = 0; p < c->C; p++) {
+        ye[p] = root_y_is_event[p] ? 1 : 0;
+        if (rr[p] >= 0 || ye[p]) rooted = true;
+    }
+    if (rooted && c->G != 1) {
+        set_err(err, HGX_ERR_INVALID, "hgx_reset: roots need a single-graph context");
+        return HGX_ERR_INVALID;
+    }
+    if (c->eng.clear() != hipSuccess || c->eng.set_roots(rr, ye) != hipSuccess ||
+        c->eng.set_root_others(nullptr, 0) != hipSuccess)
+        return dev_err(err, hipErrorUnknown, "hgx_reset");
+    reset_host_state(c, root_index, rr, ye, rooted);
+    c->root_ids_known = !rooted;   // genesis roots have no ids; the ids of a caller's roots are not known here
+    std::fill(c->root_has_x.begin(), c->root_has_x.end(), 0);
+    std::fill(c->root_has_y.begin(), c->root_has_y.end(), 0);
+    c->root_others.clear();
     return ok(err);
 }
 
@@ -1530,6 +1555,196 @@ int32_t hgx_get_frame(hgx_ctx* c, int64_t* events, int64_t events_cap, int64_t* 
     *n_others = no;
     *n_events = (int64_t)evs.size();
     for (size_t k = 0; k < evs.size() && (int64_t)k < events_cap && events; k++) events[k] = evs[k];
+    return ok(err);
+}
+
+// ---- hgx_prune_to_frame -----------------------------------------------
+// GetFrame + Reset(frame.Roots) + re-insert of frame.Events where the events live. The frame is a
+// suffix of every chain: from LastConsensusRound's witness where the chain has one, else the
+// chain's last event; the cut and the roots' Index and Round come from the host's round tables,
+// everything per event happens on the device (Engine::prune_stage / prune_to_frame).
+static const std::array<uint8_t, 64>* find_root_other(const hgx_ctx* c, const uint8_t* key32) {
+    auto it = std::lower_bound(c->root_others.begin(), c->root_others.end(), key32,
+                               [](const std::array<uint8_t, 64>& a, const uint8_t* k) { return std::memcmp(a.data(), k, 32) < 0; });
+    return it != c->root_others.end() && std::memcmp(it->data(), key32, 32) == 0 ? &*it : nullptr;
+}
+
+int32_t hgx_prune_to_frame(hgx_ctx* c, int64_t* old_gid, int64_t cap, int64_t* n_kept, hgx_error* err) {
+    if (n_kept) *n_kept = 0;
+    auto bad = [&](const char* why) {
+        set_err(err, HGX_ERR_INVALID, std::string("hgx_prune_to_frame: ") + why);
+        return HGX_ERR_INVALID;
+    };
+    if (!c || !n_kept || cap < 0 || (cap > 0 && !old_gid)) return bad("bad arguments");
+    if (c->G != 1) return bad("single-graph contexts only (roots need one graph)");
+    if (c->grp) return bad("not available on a chain-sharded context");
+    if (c->shard_world > 1) return bad("not available on a row-sharded context");
+    if (c->fo_open) return bad("a FindOrder is in progress (hgx_find_order_end first)");
+    if (!c->eng.ids_known) return bad("the events were inserted without their ids (the Root.Others keys are event ids)");
+    const GraphState& s = c->gs[0];
+    const int32_t lcr = s.has_lcr ? s.lcr : 0;
+    if (!c->divided || lcr < 0 || lcr > s.last_round || s.round_events[(size_t)lcr] == 0) {   // Store.GetRound
+        set_err(err, HGX_ERR_KEY_NOT_FOUND, std::to_string(lcr) + ", Not Found");
+        return HGX_ERR_KEY_NOT_FOUND;
+    }
+    DeviceGuard dg(c);
+    const int C = c->C;
+    // the cut and the new roots' Index and Round (Round(Root.X): from the round boundaries; -1 for
+    // an X outside the store or not yet divided, as hgx_get_frame has it)
+    std::vector<int32_t> cut((size_t)C, 0x7FFFFFFF), ri = c->root_index, rr = c->root_round;
+    std::vector<uint8_t> ye = c->root_y_ext;
+    int64_t kept = 0;
+    const int32_t R = c->rh.R;
+    for (int p = 0; p < C; p++) {
+        const int32_t len = c->chain_len[(size_t)p];
+        if (len == 0) continue;   // LastFrom is the Root: it stays
+        int32_t k = len - 1;
+        if (lcr < R && c->rh.wflag[(size_t)lcr * C + p] == 2) k = c->rh.bm[(size_t)lcr * C + p];
+        if (k < 0 || k >= len) return bad("the round tables and the chains disagree");
+        cut[(size_t)p] = c->chain_base[(size_t)p] + k;
+        kept += len - k;
+        ri[(size_t)p] = cut[(size_t)p] - 1;
+        int32_t round = -1;
+        if (k > 0 && k - 1 < c->eng.len_div(p)) {
+            int32_t lo = 0, hi = R;   // the last r with bm[r] <= k - 1 (bm rows do not decrease)
+            while (lo < hi) {
+                const int32_t mid = (lo + hi) / 2;
+                if (c->rh.bm[(size_t)mid * C + p] <= k - 1) lo = mid + 1; else hi = mid;
+            }
+            round = lo - 1;
+        }
+        rr[(size_t)p] = round;
+    }
+    hgx::Engine::PruneOut po;
+    hipError_t e = c->eng.prune_stage(cut, kept, po);
+    if (e != hipSuccess) return dev_err(err, e, "hgx_prune_to_frame");
+    // ---- everything the new state needs, in locals; nothing is changed before it is complete ----
+    bool rooted = false;
+    for (int p = 0; p < C; p++) {
+        if (c->chain_len[(size_t)p] > 0) ye[(size_t)p] = po.root_op[(size_t)p] != -1 ? 1 : 0;
+        if (rr[(size_t)p] >= 0 || ye[(size_t)p]) rooted = true;
+    }
+    bool ids_ok = c->root_ids_known;
+    std::vector<uint8_t> x_id = c->root_x_id, y_id = c->root_y_id, has_x = c->root_has_x, has_y = c->root_has_y;
+    std::vector<std::array<uint8_t, 64>> others((size_t)po.n_others);
+    for (int64_t j = 0; j < po.n_others; j++) {
+        std::array<uint8_t, 64>& o = others[(size_t)j];
+        std::memcpy(o.data(), po.oth_key.data() + 32 * j, 32);
+        if (po.oth_op[(size_t)j] >= 0) {
+            std::memcpy(o.data() + 32, po.oth_pid.data() + 32 * j, 32);
+        } else {   // HGX_ROOT_OTHER before: the entry is carried over
+            const std::array<uint8_t, 64>* old = ids_ok ? find_root_other(c, o.data()) : nullptr;
+            if (old) std::memcpy(o.data() + 32, old->data() + 32, 32);
+            else { std::memset(o.data() + 32, 0, 32); ids_ok = false; }
+        }
+    }
+    std::sort(others.begin(), others.end(), [](const std::array<uint8_t, 64>& a, const std::array<uint8_t, 64>& b) {
+        return std::memcmp(a.data(), b.data(), 32) < 0;
+    });
+    for (int p = 0; p < C && ids_ok; p++) {
+        if (c->chain_len[(size_t)p] == 0) continue;   // the whole root stays
+        const uint8_t* ids = po.root_ids.data() + 96 * (size_t)p;
+        const int32_t sp = po.root_sp[(size_t)p], op = po.root_op[(size_t)p];
+        if (sp >= 0) {
+            std::memcpy(x_id.data() + 32 * (size_t)p, ids + 32, 32);
+            has_x[(size_t)p] = 1;
+        }   // -1: the old Root.X stays
+        if (op >= 0) {
+            std::memcpy(y_id.data() + 32 * (size_t)p, ids + 64, 32);
+            has_y[(size_t)p] = 1;
+        } else if (op == -1) {
+            has_y[(size_t)p] = 0;
+        } else if (op == HGX_ROOT_OTHER) {   // the first kept event was an Others entry: its value is the new Y
+            const std::array<uint8_t, 64>* old = find_root_other(c, ids);
+            if (old) {
+                std::memcpy(y_id.data() + 32 * (size_t)p, old->data() + 32, 32);
+                has_y[(size_t)p] = 1;
+            } else {
+                ids_ok = false;
+            }
+        }   // HGX_ROOT_Y: the old Root.Y stays
+    }
+    std::vector<uint8_t> keys((size_t)po.n_others * 32);
+    for (int64_t j = 0; j < po.n_others; j++) std::memcpy(keys.data() + 32 * j, others[(size_t)j].data(), 32);
+    // the payloads restored by hgx_bootstrap follow their events (old gids ascend: a prefix has one)
+    std::vector<int64_t> pl_off;
+    std::vector<uint8_t> pl_blob;
+    if (!c->pl_off.empty()) {
+        pl_off.push_back(0);
+        for (int64_t k = 0; k < kept; k++) {
+            const size_t g = (size_t)po.old_gid[(size_t)k];
+            if (g + 1 >= c->pl_off.size()) break;
+            pl_blob.insert(pl_blob.end(), c->pl_blob.begin() + c->pl_off[g], c->pl_blob.begin() + c->pl_off[g + 1]);
+            pl_off.push_back((int64_t)pl_blob.size());
+        }
+    }
+    for (int64_t k = 0; k < kept && k < cap; k++) old_gid[k] = po.old_gid[(size_t)k];
+    // ---- the destructive part: Reset with the frame's roots, then InsertEvent for the staged frame ----
+    hgx::InsertOut out;
+    e = c->eng.prune_to_frame(rr, ye, po, out);
+    reset_host_state(c, ri.data(), rr, ye, rooted);
+    if (e != hipSuccess) return dev_err(err, e, "hgx_prune_to_frame");
+    c->others_keys = std::move(keys);
+    c->root_ids_known = ids_ok;
+    c->root_x_id = std::move(x_id);
+    c->root_y_id = std::move(y_id);
+    c->root_has_x = std::move(has_x);
+    c->root_has_y = std::move(has_y);
+    c->root_others = std::move(others);
+    hgx_error ie{};
+    int64_t inserted = 0;
+    const int32_t rc = finish_insert(c, out, &inserted, &ie);
+    // (the payloads of the accepted prefix stay addressable either way)
+    c->pl_off = std::move(pl_off);
+    c->pl_blob = std::move(pl_blob);
+    *n_kept = kept;
+    if (rc != HGX_OK || inserted != kept) {   // the validation kernels re-checked the frame: a rejection is a bug
+        set_err(err, HGX_ERR_PANIC, "hgx_prune_to_frame: frame event " + std::to_string(inserted) + " rejected: " + ie.msg);
+        return HGX_ERR_PANIC;
+    }
+    return ok(err);
+}
+
+int32_t hgx_get_root_ids(hgx_ctx* c, int32_t p, uint8_t* x_id32, int32_t* has_x, uint8_t* y_id32, int32_t* has_y,
+                         hgx_error* err) {
+    if (has_x) *has_x = 0;
+    if (has_y) *has_y = 0;
+    if (!c) {
+        set_err(err, HGX_ERR_INVALID, "hgx_get_root_ids: bad arguments");
+        return HGX_ERR_INVALID;
+    }
+    if (p < 0 || p >= c->C) {
+        set_err(err, HGX_ERR_KEY_NOT_FOUND, std::to_string(p) + ", Not Found");
+        return HGX_ERR_KEY_NOT_FOUND;
+    }
+    if (!c->root_ids_known) {
+        set_err(err, HGX_ERR_INVALID, "root ids not known");
+        return HGX_ERR_INVALID;
+    }
+    const size_t z = (size_t)p;
+    if (has_x) *has_x = c->root_has_x[z];
+    if (has_y) *has_y = c->root_has_y[z];
+    if (x_id32 && c->root_has_x[z]) std::memcpy(x_id32, c->root_x_id.data() + 32 * z, 32);
+    if (y_id32 && c->root_has_y[z]) std::memcpy(y_id32, c->root_y_id.data() + 32 * z, 32);
+    return ok(err);
+}
+
+int32_t hgx_get_root_others(hgx_ctx* c, uint8_t* event_id32, uint8_t* other_parent_id32, int64_t cap, int64_t* count,
+                            hgx_error* err) {
+    if (count) *count = 0;
+    if (!c || !count || cap < 0) {
+        set_err(err, HGX_ERR_INVALID, "hgx_get_root_others: bad arguments");
+        return HGX_ERR_INVALID;
+    }
+    if (!c->root_ids_known) {
+        set_err(err, HGX_ERR_INVALID, "root ids not known");
+        return HGX_ERR_INVALID;
+    }
+    *count = (int64_t)c->root_others.size();
+    for (int64_t j = 0; j < *count && j < cap; j++) {
+        if (event_id32) std::memcpy(event_id32 + 32 * j, c->root_others[(size_t)j].data(), 32);
+        if (other_parent_id32) std::memcpy(other_parent_id32 + 32 * j, c->root_others[(size_t)j].data() + 32, 32);
+    }
     return ok(err);
 }
 

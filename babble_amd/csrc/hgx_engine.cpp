@@ -859,6 +859,92 @@ hipError_t Engine::clear() {
     return hipStreamSynchronize(stream);
 }
 
+// ---- hgx_prune_to_frame (hgx_compact.hip) ---------------------------------
+// Stage: nothing resident is changed. The kept events' columns are gathered into pr_buf as one
+// insert batch (pr_in), and what the host needs comes back: O(kept) gids and Root.Others entries,
+// O(C) root parents and ids.
+hipError_t Engine::prune_stage(const std::vector<int32_t>& cut, int64_t n_kept, PruneOut& out) {
+    out = PruneOut();
+    pr_count = -1;
+    if ((int)cut.size() != C || n_kept < 0 || n_kept > E || !ids_known) return hipErrorInvalidValue;
+    HGX_TRY(payload_wait_S());
+    const size_t Ez = (size_t)E, K = (size_t)std::max<int64_t>(n_kept, 1), Cz = (size_t)C;
+    const size_t nparts = (Ez + 2047) / 2048 + 1;
+    // one block, every part 256-byte aligned
+    size_t total = 0;
+    auto take = [&](size_t bytes) {
+        const size_t off = total;
+        total += (bytes + 255) & ~(size_t)255;
+        return off;
+    };
+    const size_t o_scan = take(Ez * 4), o_part = take(nparts * 4), o_cut = take(Cz * 4), o_first = take(Cz * 4),
+                 o_cnt = take(8), o_cr = take(K * 4), o_idx = take(K * 4), o_sp = take(K * 4), o_op = take(K * 4),
+                 o_ntx = take(K * 4), o_old = take(K * 4), o_ts = take(K * 8), o_hash = take(K * 32),
+                 o_S = take(K * 32), o_on = take(K * 4), o_oo = take(K * 4), o_ok = take(K * 32),
+                 o_opid = take(K * 32), o_rsp = take(Cz * 4), o_rop = take(Cz * 4), o_rid = take(Cz * 96);
+    if (pr_buf.n < total) HGX_TRY(pr_buf.alloc(total));
+    uint8_t* b = pr_buf.p;
+    PruneArgs a{};
+    a.E = E; a.n_kept = n_kept; a.C = C;
+    a.g_creator = g_creator.p; a.g_index = g_index.p; a.g_sp = g_sp.p; a.g_op = g_op.p; a.g_ntx = g_ntx.p;
+    a.g_ts = g_ts.p; a.g_S = g_S.p; a.g_id = g_id.p; a.g_txnil = g_txnil.p;
+    a.cut = (const int32_t*)(b + o_cut); a.scan = (uint32_t*)(b + o_scan); a.first_gid = (int32_t*)(b + o_first);
+    a.kept_total = (uint32_t*)(b + o_cnt); a.oth_count = (uint32_t*)(b + o_cnt) + 1;
+    a.st_creator = (int32_t*)(b + o_cr); a.st_index = (int32_t*)(b + o_idx); a.st_sp = (int32_t*)(b + o_sp);
+    a.st_op = (int32_t*)(b + o_op); a.st_ntx = (int32_t*)(b + o_ntx); a.old_gid = (int32_t*)(b + o_old);
+    a.st_ts = (int64_t*)(b + o_ts); a.st_hash = b + o_hash; a.st_S = b + o_S;
+    a.oth_new = (int32_t*)(b + o_on); a.oth_op = (int32_t*)(b + o_oo); a.oth_key = b + o_ok; a.oth_pid = b + o_opid;
+    a.root_sp = (int32_t*)(b + o_rsp); a.root_op = (int32_t*)(b + o_rop); a.root_ids = b + o_rid;
+    out.old_gid.resize((size_t)n_kept);
+    out.root_sp.resize(Cz);
+    out.root_op.resize(Cz);
+    out.root_ids.resize(Cz * 96);
+    HGX_TRY(hipMemcpyAsync(b + o_cut, cut.data(), Cz * 4, hipMemcpyHostToDevice, stream));
+    HGX_TRY(hipMemsetAsync(b + o_first, 0xFF, Cz * 4, stream));
+    HGX_TRY(hipMemsetAsync(b + o_cnt, 0, 8, stream));
+    launch_prune(stream, a, (uint32_t*)(b + o_part));
+    HGX_TRY(hipGetLastError());
+    uint32_t cnt[2] = {0, 0};
+    HGX_TRY(hipMemcpyAsync(cnt, b + o_cnt, 8, hipMemcpyDeviceToHost, stream));
+    if (n_kept) HGX_TRY(hipMemcpyAsync(out.old_gid.data(), a.old_gid, (size_t)n_kept * 4, hipMemcpyDeviceToHost, stream));
+    HGX_TRY(hipMemcpyAsync(out.root_sp.data(), a.root_sp, Cz * 4, hipMemcpyDeviceToHost, stream));
+    HGX_TRY(hipMemcpyAsync(out.root_op.data(), a.root_op, Cz * 4, hipMemcpyDeviceToHost, stream));
+    HGX_TRY(hipMemcpyAsync(out.root_ids.data(), a.root_ids, Cz * 96, hipMemcpyDeviceToHost, stream));
+    HGX_TRY(hipStreamSynchronize(stream));
+    if ((int64_t)cnt[0] != n_kept || (int64_t)cnt[1] > n_kept) return hipErrorInvalidValue;   // host and device disagree on the cut
+    const size_t no = cnt[1];
+    out.n_others = (int64_t)no;
+    out.oth_new.resize(no);
+    out.oth_op.resize(no);
+    out.oth_key.resize(no * 32);
+    out.oth_pid.resize(no * 32);
+    if (no) {
+        HGX_TRY(hipMemcpyAsync(out.oth_new.data(), a.oth_new, no * 4, hipMemcpyDeviceToHost, stream));
+        HGX_TRY(hipMemcpyAsync(out.oth_op.data(), a.oth_op, no * 4, hipMemcpyDeviceToHost, stream));
+        HGX_TRY(hipMemcpyAsync(out.oth_key.data(), a.oth_key, no * 32, hipMemcpyDeviceToHost, stream));
+        HGX_TRY(hipMemcpyAsync(out.oth_pid.data(), a.oth_pid, no * 32, hipMemcpyDeviceToHost, stream));
+        HGX_TRY(hipStreamSynchronize(stream));
+    }
+    pr_in = InsertIn{};
+    pr_in.creator = a.st_creator; pr_in.index32 = a.st_index; pr_in.sp32 = a.st_sp; pr_in.op32 = a.st_op;
+    pr_in.ts = a.st_ts; pr_in.hash = a.st_hash; pr_in.S = a.st_S; pr_in.ntx = a.st_ntx;
+    pr_count = n_kept;
+    return hipSuccess;
+}
+
+// Commit: Reset with the new roots and Root.Others keys, then InsertEvent for the staged batch (the
+// validation kernels re-check the frame; out.code != 0 is a bug the caller reports)
+hipError_t Engine::prune_to_frame(const std::vector<int32_t>& root_round, const std::vector<uint8_t>& y_ext,
+                                  const PruneOut& st, InsertOut& out) {
+    if (pr_count < 0) return hipErrorInvalidValue;
+    const int64_t count = pr_count;
+    pr_count = -1;
+    HGX_TRY(clear());
+    HGX_TRY(set_roots(root_round, y_ext));
+    HGX_TRY(set_root_others(st.oth_key.data(), st.n_others));
+    return insert(pr_in, count, out);
+}
+
 hipError_t Engine::get_ids(int64_t first, int64_t count, uint8_t* out32) {
     if (!ids_known || first < 0 || first + count > E) return hipErrorInvalidValue;
     if (count <= 0) return hipSuccess;

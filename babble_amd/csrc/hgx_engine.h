@@ -192,6 +192,25 @@ class Engine {
     hipError_t insert_split_begin_packed(const Packed& pk, int64_t count, InsertOut& out);
     // forget every event (a fresh NewHashgraph); allocations are kept
     hipError_t clear();
+    // hgx_prune_to_frame (hgx_compact.hip) in two steps. prune_stage changes nothing
+    // resident: the events with Index >= cut[creator] (n_kept of them, counted by the caller) are
+    // gathered into a staging block as one insert batch with renumbered parents, and their old gids,
+    // the Root.Others entries and the new roots' parents and ids are read back (O(kept + C) bytes).
+    // prune_to_frame then clears the store, installs the roots and the Others keys and re-inserts
+    // the staged batch through the validation kernels.
+    struct PruneOut {
+        std::vector<int32_t> old_gid;            // [n_kept] old gid of each new gid
+        std::vector<int32_t> root_sp, root_op;   // [C] parents of each chain's first kept event (-1 without one)
+        std::vector<uint8_t> root_ids;           // [C][3][32] ids of that event, its self- and other-parent (zero: none)
+        int64_t n_others = 0;                    // Root.Others entries, in no particular order:
+        std::vector<int32_t> oth_new, oth_op;    // the event's new gid, its old other-parent (gid or HGX_ROOT_OTHER)
+        std::vector<uint8_t> oth_key, oth_pid;   // the event's id and its other-parent's (zero for a code)
+    };
+    hipError_t prune_stage(const std::vector<int32_t>& cut, int64_t n_kept, PruneOut& out);
+    hipError_t prune_to_frame(const std::vector<int32_t>& root_round, const std::vector<uint8_t>& y_ext,
+                              const PruneOut& st, InsertOut& out);
+    // chain lengths at the last DivideRounds (events past them have no round yet)
+    int32_t len_div(int chain) const { return laid_out && chain < (int)h_len_div.size() ? h_len_div[(size_t)chain] : 0; }
     // per-event columns (gid order) for the host-side getters
     hipError_t get_events(std::vector<int32_t>& creator, std::vector<int32_t>& index, std::vector<int32_t>& sp,
                           std::vector<int32_t>& op);
@@ -351,6 +370,10 @@ class Engine {
     DBuf<int64_t> st_exc_pos;
     DBuf<int32_t> st_exc_sp, st_exc_op;
     DBuf<uint8_t> st_coin;
+    // hgx_prune_to_frame: the scan, the staged batch and the read-back tables (one block)
+    DBuf<uint8_t> pr_buf;
+    InsertIn pr_in{};
+    int64_t pr_count = -1;   // events staged by prune_stage (-1: none)
     // batches of at most kPackEvents from host memory: the columns packed in one pinned buffer,
     // one H2D copy into st_pack
     static constexpr int64_t kPackEvents = 65536;

@@ -344,4 +344,31 @@ void launch_unpack_packed(hipStream_t s, int64_t m, int64_t E0, const uint16_t* 
                           const uint16_t* opb, int64_t n_exc, const int64_t* exc_pos, const int32_t* exc_sp,
                           const int32_t* exc_op, int32_t* cr, int32_t* sp, int32_t* op);
 
+// exclusive scan of `total` u32 in place (hgx_kernels.hip); part: (total + 2047) / 2048 words
+void launch_scan_u32(hipStream_t s, uint32_t* buf, int64_t total, uint32_t* part);
+
+// hgx_prune_to_frame (hgx_compact.hip): the resident columns, the per-chain cut, and where the
+// kept events' columns (one hgx_events32-style insert batch), old gids, Root.Others entries and
+// the new roots' parents and ids go. Every output array holds n_kept (others, staging) or C entries.
+struct PruneArgs {
+    int64_t E, n_kept;
+    int C;
+    const int32_t *g_creator, *g_index, *g_sp, *g_op, *g_ntx;
+    const int64_t* g_ts;
+    const uint8_t *g_S, *g_id, *g_txnil;
+    const int32_t* cut;        // [C] smallest kept Index of each chain (INT32_MAX: none)
+    uint32_t* scan;            // [E] keep flags, then their exclusive scan (the new gids)
+    int32_t* first_gid;        // [C] the first kept event of each chain (-1: none; preset to -1)
+    uint32_t* kept_total;      // the scan's total (checked against n_kept before anything is dropped)
+    int32_t *st_creator, *st_index, *st_sp, *st_op, *st_ntx, *old_gid;
+    int64_t* st_ts;
+    uint8_t *st_hash, *st_S;
+    uint32_t* oth_count;       // Root.Others entries emitted (preset to 0), in no particular order:
+    int32_t *oth_new, *oth_op; // the event's new gid and its old other-parent (a gid or HGX_ROOT_OTHER)
+    uint8_t *oth_key, *oth_pid;   // the event's id and its other-parent's (zero when that is a code)
+    int32_t *root_sp, *root_op;   // [C] the first kept event's parents (old gids / codes)
+    uint8_t* root_ids;            // [C][3][32] ids of that event, its self-parent and its other-parent
+};
+void launch_prune(hipStream_t s, const PruneArgs& a, uint32_t* scan_part);
+
 }  // namespace hgx

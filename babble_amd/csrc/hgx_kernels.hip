@@ -2536,11 +2536,15 @@ void launch_minmax(hipStream_t s, const DevArrays& a, int32_t m) {
                        (unsigned long long*)a.minmax);
 }
 
-static void scan_u32(hipStream_t s, const DevArrays& a, uint32_t* buf, int64_t total) {
+void launch_scan_u32(hipStream_t s, uint32_t* buf, int64_t total, uint32_t* part) {
     const int nparts = (int)((total + kScanChunk - 1) / kScanChunk);
-    hipLaunchKernelGGL(k_scan_reduce, dim3(nparts), dim3(256), 0, s, buf, total, a.scan_part);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, s, a.scan_part, nparts);
-    hipLaunchKernelGGL(k_scan_down, dim3(nparts), dim3(256), 0, s, buf, total, a.scan_part);
+    hipLaunchKernelGGL(k_scan_reduce, dim3(nparts), dim3(256), 0, s, buf, total, part);
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, s, part, nparts);
+    hipLaunchKernelGGL(k_scan_down, dim3(nparts), dim3(256), 0, s, buf, total, part);
+}
+
+static void scan_u32(hipStream_t s, const DevArrays& a, uint32_t* buf, int64_t total) {
+    launch_scan_u32(s, buf, total, a.scan_part);
 }
 
 static void radix_pass(hipStream_t s, const DevArrays& a, int32_t m, int shift, const uint64_t* kin,

@@ -538,6 +538,31 @@ class Hashgraph:
                     events=[int(x) for x in ev[:ne.value]],
                     others={int(oe[k]): int(op[k]) for k in range(no.value)})
 
+    def PruneToFrame(self) -> np.ndarray:
+        """The resident hashgraph cut down to its last frame on the device (hgx_prune_to_frame):
+        GetFrame, Reset(frame roots) and the re-insert of the frame's events in one call, with no
+        event crossing PCIe. Returns old_gid: the old gid of each new gid. RunConsensus next."""
+        nk = C.c_int64()
+        old = np.zeros(max(1, self.num_events()), np.int64)
+        self._call(lambda ctx, e: self.L.hgx_prune_to_frame(ctx, ptr(old), old.size, C.byref(nk), e))
+        return old[:nk.value].copy()
+
+    def GetRootIds(self, participant: int) -> dict:
+        """The 32-byte ids of the participant's Root.X and Root.Y (None for ""), known while every
+        root traces back to genesis through PruneToFrame (hgx_get_root_ids)."""
+        x, y = np.zeros(32, np.uint8), np.zeros(32, np.uint8)
+        hx, hy = C.c_int32(), C.c_int32()
+        self._call(lambda ctx, e: self.L.hgx_get_root_ids(ctx, participant, ptr(x), C.byref(hx), ptr(y), C.byref(hy), e))
+        return dict(X=x.tobytes() if hx.value else None, Y=y.tobytes() if hy.value else None)
+
+    def GetRootOthers(self) -> List[tuple]:
+        """The roots' Others pairs (event id, other-parent id), sorted by event id (hgx_get_root_others)."""
+        cnt = C.c_int64()
+        self._call(lambda ctx, e: self.L.hgx_get_root_others(ctx, None, None, 0, C.byref(cnt), e))
+        k, v = np.zeros((max(1, cnt.value), 32), np.uint8), np.zeros((max(1, cnt.value), 32), np.uint8)
+        self._call(lambda ctx, e: self.L.hgx_get_root_others(ctx, ptr(k), ptr(v), cnt.value, C.byref(cnt), e))
+        return [(k[j].tobytes(), v[j].tobytes()) for j in range(cnt.value)]
+
     # ------------------------------------------------------------------ row-sharded graph
     def set_shard(self, rank: int, world: int):
         """One graph row-sharded over `world` ranks (hgx_set_shard)."""

@@ -36,7 +36,8 @@
 extern "C" {
 #endif
 
-#define HGX_ABI_VERSION 6   /* (still 6 with hgx_insert_event_bodies, hgx_event_json_batch and hgx_batch_levels:
+#define HGX_ABI_VERSION 6   /* (still 6 with hgx_insert_event_bodies, hgx_event_json_batch and hgx_batch_levels,
+                                 and with hgx_prune_to_frame, hgx_get_root_ids and hgx_get_root_others:
                                  purely additive, no existing entry or structure changed)
                               6: hgx_host_alloc / hgx_host_free (page-locked caller buffers);
                               5: hgx_events_packed (hgx_insert_events_packed, hgx_insert_and_run_packed,
@@ -389,6 +390,35 @@ int32_t hgx_set_root_others(hgx_ctx* ctx, const uint8_t* event_hash32, int64_t c
 int32_t hgx_get_frame(hgx_ctx* ctx, int64_t* events, int64_t events_cap, int64_t* n_events, int64_t* root_x,
                       int64_t* root_y, int32_t* root_index, int32_t* root_round, int64_t* others_event,
                       int64_t* others_parent, int64_t others_cap, int64_t* n_others, hgx_error* err);
+/* The resident hashgraph cut down to its last frame where it lives: the context
+ * ends in the state that hgx_get_frame, hgx_reset(frame roots), hgx_set_root_others(ids of the
+ * frame's Others events) and hgx_insert_events of the frame's events (in frame order, which is
+ * ascending old gid) leave, without the caller holding any event and with nothing proportional to
+ * the resident events crossing PCIe. The kept events keep their ids, timestamps, S, coin,
+ * ntx / tx_nil and payloads (hgx_get_event_payload); new gid k is the position in the frame. Parents
+ * as InsertEvent resolves them after a Reset (hashgraph.go:404-445): a kept parent -> its new gid;
+ * the self-parent of a creator's first kept event -> -1 (the new Root.X); an other-parent outside
+ * the frame -> HGX_ROOT_Y for that first event, else HGX_ROOT_OTHER (the event is a Root.Others key);
+ * the codes of an already rooted context by the same rules. old_gid[0 .. min(cap, *n_kept)) gets the
+ * old gid of each new gid, *n_kept the full count. Consensus is not run (hgx_run_consensus next, as
+ * after a Reset). Kept and forgotten as by hgx_reset; the participant keys and the commit callback
+ * stay. Refusals leave the context untouched: HGX_ERR_KEY_NOT_FOUND "<r>, Not Found" where
+ * hgx_get_frame gives it; HGX_ERR_INVALID "<reason>" for a batch (G > 1), chain-sharded or
+ * row-sharded context, a context whose event ids are not known (hgx_events32 / packed inserts, a
+ * checkpoint without ids: the Others keys are event ids), and for a NULL ctx or n_kept. A frame
+ * event the validation kernels reject is reported as HGX_ERR_PANIC (a bug; the events up to it are
+ * resident). */
+int32_t hgx_prune_to_frame(hgx_ctx* ctx, int64_t* old_gid, int64_t cap, int64_t* n_kept, hgx_error* err);
+/* The 32-byte ids of the current roots' X and Y (has_x / has_y = 0 for "": a genesis root) and the
+ * roots' Others pairs (event id, other-parent id), sorted by event id; *count in full, the arrays
+ * get the first `cap`. hgx_prune_to_frame gathers them before the dropped events go, and carries
+ * them over a further prune (a participant without events keeps its whole root). Known only while
+ * every root traces back to genesis through prunes: after the caller's own hgx_reset with roots,
+ * or a rooted hgx_bootstrap, both return HGX_ERR_INVALID "root ids not known". */
+int32_t hgx_get_root_ids(hgx_ctx* ctx, int32_t participant, uint8_t* x_id32, int32_t* has_x, uint8_t* y_id32,
+                         int32_t* has_y, hgx_error* err);
+int32_t hgx_get_root_others(hgx_ctx* ctx, uint8_t* event_id32, uint8_t* other_parent_id32, int64_t cap,
+                            int64_t* count, hgx_error* err);
 
 /* ---- Hashgraph state (hashgraph.go:15-37) --------------------------------- */
 int64_t hgx_num_events(hgx_ctx* ctx);
