@@ -129,6 +129,7 @@ def lib():
     for nm in ("hgx_insert_events_verified", "hgx_insert_events_verified_device"):
         _sig(L, nm, i32, [p, C.POINTER(hgx_events), p, p, i64, C.POINTER(C.c_int64), E])
     _sig(L, "hgx_insert_event_bodies", i32, [p, C.POINTER(hgx_event_bodies), i64, p, C.POINTER(C.c_int64), E])
+    _sig(L, "hgx_insert_event_bodies_ext", i32, [p, C.POINTER(hgx_event_bodies), p, i64, p, C.POINTER(C.c_int64), E])
     _sig(L, "hgx_event_json_batch", i32, [i32, C.POINTER(hgx_event_bodies), i64, p, i32, p, p, p, i64, p, E])
     _sig(L, "hgx_batch_levels", i32, [p, p, i64, i64, p, C.POINTER(C.c_int32), E])
     _sig(L, "hgx_reset_consensus", i32, [p])
@@ -205,6 +206,7 @@ def lib():
     _sig(L, "hgx_prune_to_frame", i32, [p, p, i64, C.POINTER(C.c_int64), E])
     _sig(L, "hgx_get_root_ids", i32, [p, i32, p, C.POINTER(C.c_int32), p, C.POINTER(C.c_int32), E])
     _sig(L, "hgx_get_root_others", i32, [p, p, p, i64, C.POINTER(C.c_int64), E])
+    _sig(L, "hgx_set_root_ids", i32, [p, p, p, p, p, p, p, i64, E])
     _sig(L, "hgx_shard_values", i64, [p, i32])
     _sig(L, "hgx_shard_export", i32, [p, p, i32])
     _sig(L, "hgx_shard_import", i32, [p, i32, p, i32])

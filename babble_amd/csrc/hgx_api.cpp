@@ -864,9 +864,10 @@ int32_t hgx_insert_events_verified_device(hgx_ctx* c, const hgx_events* ev, cons
 // InsertEvent with Event.Hash and Event.Verify on the device, from the events' fields (DESIGN.md
 // §3.10). An event without a text (creator without a key, a parent that is neither "" nor an earlier
 // gid) cuts the batch: the prefix goes through the body path, then that event through the plain insert
-// checks, which reject it with the reference's parent-check error.
-int32_t hgx_insert_event_bodies(hgx_ctx* c, const hgx_event_bodies* evb, int64_t count, uint8_t* out_id32,
-                                int64_t* n_inserted, hgx_error* err) {
+// checks, which reject it with the reference's parent-check error. On a context with root ids
+//  self-parent -1, HGX_ROOT_Y and HGX_ROOT_OTHER print the roots' ids.
+int32_t hgx_insert_event_bodies_ext(hgx_ctx* c, const hgx_event_bodies* evb, const uint8_t* other_parent_id32,
+                                    int64_t count, uint8_t* out_id32, int64_t* n_inserted, hgx_error* err) {
     const std::string who = "hgx_insert_event_bodies: ";
     auto bad = [&](const std::string& why) {
         set_err(err, HGX_ERR_INVALID, who + why);
@@ -881,13 +882,15 @@ int32_t hgx_insert_event_bodies(hgx_ctx* c, const hgx_event_bodies* evb, int64_t
     if (!c) return bad("bad arguments");
     if (c->grp) return bad("not available on a chain-sharded context");
     if (c->shard_world > 1) return bad("not available on a row-sharded context");
-    if (c->rooted) return bad("not after hgx_reset (a Root's events have no id in the store)");
+    if (c->rooted && !c->root_ids_known) return bad("not after hgx_reset without root ids (hgx_set_root_ids)");
     if (!c->eng.keys_set) return bad("participant keys not set");
     if (!c->eng.ids_known) return bad("ids not known (the context holds events inserted without their ids)");
     DeviceGuard dg(c);
-    const int64_t cut = hgx::bodies_first_unencodable(ev, count, c->E, c->C);
+    const bool root_ids = c->eng.root_ids_set;   // else the codes below -1 have no text, as on an unrooted context
+    const int64_t cut = hgx::bodies_first_unencodable(ev, count, c->E, c->C, root_ids ? c->root_has_y.data() : nullptr,
+                                                      other_parent_id32 != nullptr);
     hgx::InsertOut out;
-    hipError_t e = c->eng.insert_bodies(ev, txi, cut, out_id32, out);
+    hipError_t e = c->eng.insert_bodies(ev, txi, cut, other_parent_id32, out_id32, out);
     if (e != hipSuccess) return dev_err(err, e, "hgx_insert_event_bodies");
     if (out.code == hgx::INS_OK && cut < count) {
         // the cut event's own checks (it cannot pass them: its creator or a parent is unknown)
@@ -903,6 +906,11 @@ int32_t hgx_insert_event_bodies(hgx_ctx* c, const hgx_event_bodies* evb, int64_t
         out.accepted += ok_before;
     }
     return finish_insert(c, out, n_inserted, err);
+}
+
+int32_t hgx_insert_event_bodies(hgx_ctx* c, const hgx_event_bodies* evb, int64_t count, uint8_t* out_id32,
+                                int64_t* n_inserted, hgx_error* err) {
+    return hgx_insert_event_bodies_ext(c, evb, nullptr, count, out_id32, n_inserted, err);
 }
 
 // Core.Sync's loop (node/core.go:199-211) over a SyncResponse's WireEvents: ReadWireInfo
@@ -1023,6 +1031,13 @@ int32_t hgx_insert_events_device(hgx_ctx* c, const hgx_events* ev, int64_t count
     return insert_events_device_one(c, ev, count, n_inserted, err);
 }
 
+// the roots' ids on the device follow the host's; nothing installed while they are not known
+static hipError_t sync_root_ids(hgx_ctx* c) {
+    if (!c->root_ids_known) return c->eng.set_root_ids(nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+    return c->eng.set_root_ids(c->root_x_id.data(), c->root_has_x.data(), c->root_y_id.data(), c->root_has_y.data(),
+                               c->root_others.empty() ? nullptr : c->root_others[0].data(), (int64_t)c->root_others.size());
+}
+
 static int32_t clear_one(hgx_ctx* c) {
     if (!c) return HGX_ERR_INVALID;
     DeviceGuard dg(c);
@@ -1051,6 +1066,7 @@ static int32_t clear_one(hgx_ctx* c) {
     std::fill(c->root_has_x.begin(), c->root_has_x.end(), 0);
     std::fill(c->root_has_y.begin(), c->root_has_y.end(), 0);
     c->root_others.clear();
+    if (c->eng.root_ids_set && sync_root_ids(c) != hipSuccess) return HGX_ERR_DEVICE;
     if (c->rooted) {   // a fresh NewHashgraph has genesis roots
         std::fill(c->root_index.begin(), c->root_index.end(), -1);
         std::fill(c->root_round.begin(), c->root_round.end(), -1);
@@ -1481,6 +1497,7 @@ int32_t hgx_reset(hgx_ctx* c, const int32_t* root_index, const int32_t* root_rou
     std::fill(c->root_has_x.begin(), c->root_has_x.end(), 0);
     std::fill(c->root_has_y.begin(), c->root_has_y.end(), 0);
     c->root_others.clear();
+    if (c->eng.root_ids_set && sync_root_ids(c) != hipSuccess) return dev_err(err, hipErrorUnknown, "hgx_reset");
     return ok(err);
 }
 
@@ -1691,6 +1708,7 @@ int32_t hgx_prune_to_frame(hgx_ctx* c, int64_t* old_gid, int64_t cap, int64_t* n
     c->root_has_x = std::move(has_x);
     c->root_has_y = std::move(has_y);
     c->root_others = std::move(others);
+    if (sync_root_ids(c) != hipSuccess) return dev_err(err, hipErrorUnknown, "hgx_prune_to_frame");
     hgx_error ie{};
     int64_t inserted = 0;
     const int32_t rc = finish_insert(c, out, &inserted, &ie);
@@ -1745,6 +1763,62 @@ int32_t hgx_get_root_others(hgx_ctx* c, uint8_t* event_id32, uint8_t* other_pare
         if (event_id32) std::memcpy(event_id32 + 32 * j, c->root_others[(size_t)j].data(), 32);
         if (other_parent_id32) std::memcpy(other_parent_id32 + 32 * j, c->root_others[(size_t)j].data() + 32, 32);
     }
+    return ok(err);
+}
+
+// The ids of roots the caller installed with hgx_reset: Root.X / Root.Y per
+// participant and the Others pairs, whose keys replace those of hgx_set_root_others. Everything is
+// checked and built in locals first; a refusal changes nothing.
+int32_t hgx_set_root_ids(hgx_ctx* c, const uint8_t* x_id32, const int32_t* has_x, const uint8_t* y_id32,
+                         const int32_t* has_y, const uint8_t* others_event_id32, const uint8_t* others_parent_id32,
+                         int64_t n_others, hgx_error* err) {
+    auto bad = [&](const std::string& why) {
+        set_err(err, HGX_ERR_INVALID, "hgx_set_root_ids: " + why);
+        return (int32_t)HGX_ERR_INVALID;
+    };
+    if (!c || !has_x || !has_y || n_others < 0 || (n_others > 0 && (!others_event_id32 || !others_parent_id32)))
+        return bad("bad arguments");
+    if (c->G != 1) return bad("single-graph contexts only (roots need one graph)");
+    if (c->grp) return bad("not available on a chain-sharded context");
+    if (c->shard_world > 1) return bad("not available on a row-sharded context");
+    if (c->E > 0) return bad("events are already resident (install the root ids before the first insert)");
+    if (!c->rooted && n_others > 0) return bad("no roots installed (hgx_reset)");
+    const size_t Cz = (size_t)c->C;
+    std::vector<uint8_t> hx(Cz), hy(Cz), xi(Cz * 32, 0), yi(Cz * 32, 0);
+    for (size_t p = 0; p < Cz; p++) {
+        hx[p] = has_x[p] ? 1 : 0;
+        hy[p] = has_y[p] ? 1 : 0;
+        if (hy[p] != c->root_y_ext[p])
+            return bad("has_y[" + std::to_string(p) + "] disagrees with the root's root_y_is_event");
+        if ((hx[p] && !x_id32) || (hy[p] && !y_id32)) return bad("bad arguments");
+        if (hx[p]) std::memcpy(xi.data() + 32 * p, x_id32 + 32 * p, 32);
+        if (hy[p]) std::memcpy(yi.data() + 32 * p, y_id32 + 32 * p, 32);
+    }
+    std::vector<std::array<uint8_t, 64>> others((size_t)n_others);
+    for (int64_t j = 0; j < n_others; j++) {
+        std::memcpy(others[(size_t)j].data(), others_event_id32 + 32 * j, 32);
+        std::memcpy(others[(size_t)j].data() + 32, others_parent_id32 + 32 * j, 32);
+    }
+    std::sort(others.begin(), others.end(), [](const std::array<uint8_t, 64>& a, const std::array<uint8_t, 64>& b) {
+        return std::memcmp(a.data(), b.data(), 32) < 0;
+    });
+    for (size_t j = 1; j < others.size(); j++)
+        if (std::memcmp(others[j - 1].data(), others[j].data(), 32) == 0) return bad("an event id appears twice in the pairs");
+    std::vector<uint8_t> keys((size_t)n_others * 32);
+    for (int64_t j = 0; j < n_others; j++) std::memcpy(keys.data() + 32 * j, others[(size_t)j].data(), 32);
+    DeviceGuard dg(c);
+    hipError_t e = c->eng.set_root_others(keys.data(), n_others);
+    if (e == hipSuccess)
+        e = c->eng.set_root_ids(xi.data(), hx.data(), yi.data(), hy.data(), others.empty() ? nullptr : others[0].data(),
+                                n_others);
+    if (e != hipSuccess) return dev_err(err, e, "hgx_set_root_ids");
+    c->others_keys = std::move(keys);
+    c->root_ids_known = true;
+    c->root_x_id = std::move(xi);
+    c->root_y_id = std::move(yi);
+    c->root_has_x = std::move(hx);
+    c->root_has_y = std::move(hy);
+    c->root_others = std::move(others);
     return ok(err);
 }
 

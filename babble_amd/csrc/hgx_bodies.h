@@ -34,8 +34,11 @@ int64_t batch_levels(const int64_t* sp, const int64_t* op, int64_t count, int64_
                      int32_t* n_levels);
 
 // The first position whose event has no Go-JSON text: a creator outside [0, n_keys) or a parent that
-// is neither -1 nor an earlier gid (count if there is none).
-int64_t bodies_first_unencodable(const BodiesIn& ev, int64_t count, int64_t base, int32_t n_keys);
+// is neither -1 nor an earlier gid (count if there is none). On a context with root ids (root_has_y
+// not null: [n_keys] flags) two other-parent codes have a text as well: HGX_ROOT_Y
+// where the creator's root has a Y, and HGX_ROOT_OTHER when the caller supplied the ids (have_op_ids).
+int64_t bodies_first_unencodable(const BodiesIn& ev, int64_t count, int64_t base, int32_t n_keys,
+                                 const uint8_t* root_has_y = nullptr, bool have_op_ids = false);
 
 // One past the last event of the chunk that starts at lo: at most kBodyChunkEvents events and
 // kBodyChunkBytes of JSON by the per-event bound (at least one event). *bound = the chunk's bound with

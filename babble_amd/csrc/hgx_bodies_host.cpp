@@ -43,12 +43,16 @@ int64_t batch_levels(const int64_t* sp, const int64_t* op, int64_t count, int64_
     return -1;
 }
 
-int64_t bodies_first_unencodable(const BodiesIn& ev, int64_t count, int64_t base, int32_t n_keys) {
+int64_t bodies_first_unencodable(const BodiesIn& ev, int64_t count, int64_t base, int32_t n_keys,
+                                 const uint8_t* root_has_y, bool have_op_ids) {
     for (int64_t k = 0; k < count; k++) {
         const int64_t g = base + k;
-        if (ev.creator[k] < 0 || ev.creator[k] >= n_keys || ev.sp[k] < -1 || ev.sp[k] >= g || ev.op[k] < -1 ||
-            ev.op[k] >= g)
-            return k;
+        if (ev.creator[k] < 0 || ev.creator[k] >= n_keys || ev.sp[k] < -1 || ev.sp[k] >= g || ev.op[k] >= g) return k;
+        if (ev.op[k] < -1) {
+            const bool has_text = root_has_y && ((ev.op[k] == HGX_ROOT_Y && root_has_y[ev.creator[k]]) ||
+                                                 (ev.op[k] == HGX_ROOT_OTHER && have_op_ids));
+            if (!has_text) return k;
+        }
     }
     return count;
 }

@@ -988,6 +988,44 @@ hipError_t Engine::set_root_others(const uint8_t* keys32, int64_t count) {
     return hipStreamSynchronize(stream);
 }
 
+// The roots' ids for the event-body encoder: one block of per-chain rows and the sorted Others pairs
+// (the keys as set_root_others stores them, so the two binary searches order alike)
+hipError_t Engine::set_root_ids(const uint8_t* x_id32, const uint8_t* has_x, const uint8_t* y_id32, const uint8_t* has_y,
+                                const uint8_t* pairs64, int64_t n_pairs) {
+    const size_t Cz = (size_t)C;
+    std::vector<uint8_t> tab(66 * Cz, 0);
+    bool any = n_pairs > 0;
+    for (size_t p = 0; p < Cz; p++) {
+        if (has_x && has_x[p]) {
+            std::memcpy(tab.data() + 32 * p, x_id32 + 32 * p, 32);
+            tab[64 * Cz + p] = 1;
+            any = true;
+        }
+        if (has_y && has_y[p]) {
+            std::memcpy(tab.data() + 32 * Cz + 32 * p, y_id32 + 32 * p, 32);
+            tab[65 * Cz + p] = 1;
+            any = true;
+        }
+    }
+    std::vector<uint64_t> pr((size_t)n_pairs * 8);
+    for (int64_t i = 0; i < n_pairs; i++) {
+        for (int w = 0; w < 4; w++) {
+            uint64_t x = 0;
+            for (int b = 0; b < 8; b++) x = (x << 8) | pairs64[64 * i + 8 * w + b];
+            pr[(size_t)i * 8 + w] = x;
+        }
+        std::memcpy(&pr[(size_t)i * 8 + 4], pairs64 + 64 * i + 32, 32);
+    }
+    if (root_tab_d.n < tab.size()) HGX_TRY(root_tab_d.alloc(tab.size()));
+    if (root_pairs_d.n < std::max<size_t>(8, pr.size())) HGX_TRY(root_pairs_d.alloc(std::max<size_t>(8, pr.size())));
+    HGX_TRY(hipMemcpyAsync(root_tab_d.p, tab.data(), tab.size(), hipMemcpyHostToDevice, stream));
+    if (n_pairs) HGX_TRY(hipMemcpyAsync(root_pairs_d.p, pr.data(), pr.size() * 8, hipMemcpyHostToDevice, stream));
+    HGX_TRY(hipStreamSynchronize(stream));
+    n_root_pairs = n_pairs;
+    root_ids_set = any;
+    return hipSuccess;
+}
+
 hipError_t Engine::round_first_gids(int32_t r0, std::vector<int32_t>& out) {
     out.assign((size_t)std::max(0, R - r0), 0x7FFFFFFF);
     if (R <= r0) return hipSuccess;

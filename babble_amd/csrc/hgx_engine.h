@@ -141,10 +141,21 @@ class Engine {
     // the same with Event.Hash and Event.Verify's digest computed here from the events' fields (host
     // columns): Go-JSON texts, ids in dependency order, body digests, then insert_verified, in internal
     // chunks (hgx_goenc_dev.hip). txi: bodies_check's. out_id32 (host, may be null)
-    // gets the accepted prefix's ids.
-    hipError_t insert_bodies(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count, uint8_t* out_id32,
-                             InsertOut& out);
+    // gets the accepted prefix's ids. op_id32 (host, may be null): the ids of the HGX_ROOT_OTHER
+    // other-parents, 32 bytes per event (read on a context with root ids only).
+    hipError_t insert_bodies(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count, const uint8_t* op_id32,
+                             uint8_t* out_id32, InsertOut& out);
     EvScratch* ev_scratch = nullptr;
+    // The roots' ids on the device: Root.X / Root.Y per chain and the Root.Others
+    // pairs sorted by event id, the text of the parents that are in no id column. has_x / has_y: [C];
+    // pairs: (event id, other-parent id) sorted by event id. root_ids_set = some id is installed (a
+    // context without one encodes exactly as an unrooted one).
+    hipError_t set_root_ids(const uint8_t* x_id32, const uint8_t* has_x, const uint8_t* y_id32, const uint8_t* has_y,
+                            const uint8_t* pairs64, int64_t n_pairs);
+    bool root_ids_set = false;
+    DBuf<uint8_t> root_tab_d;      // x_id [C][32] | y_id [C][32] | has_x [C] | has_y [C]
+    DBuf<uint64_t> root_pairs_d;   // [n_root_pairs][8]: the key as 4 big-endian words, the value's 32 bytes
+    int64_t n_root_pairs = 0;
     // participants' public keys (65 bytes each, C of them): device window tables built once
     hipError_t set_keys(const uint8_t* keys65);
     bool keys_set = false;

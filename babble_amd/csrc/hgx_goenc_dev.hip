@@ -228,6 +228,16 @@ struct EvCols {
     const uint8_t* tx_bytes;
     const uint8_t* keys65;   // [n_keys][65]
     const uint8_t *sp_id, *op_id;   // [m][32] the parents' ids, or null: the slots stay open
+    const uint8_t* root_has_x;      // [n_keys] the creator's Root.X has an id (§3.12), or null: no root ids
+};
+
+// The roots' ids (Engine::set_root_ids, §3.12): the text of parents that are in no id column. All null
+// on a context without root ids.
+struct RootIds {
+    const uint8_t *x_id, *y_id;      // [C][32]
+    const uint8_t *has_x, *has_y;    // [C]
+    const uint64_t* pairs;           // [n_pairs][8] Root.Others: key (4 big-endian words), value (32 bytes)
+    int64_t n_pairs;
 };
 
 // Event k's text into the sink; slot = where the self-parent string starts, body_end = one past the
@@ -252,7 +262,8 @@ __host__ __device__ __forceinline__ void encode_event(S& s, const EvCols& c, int
     }
     put_str(s, ",\"Parents\":[\"");
     slot = s.n;
-    if (c.sp[k] != -1) {
+    // ("" for -1, except on a context with root ids where the creator's Root.X has one)
+    if (c.sp[k] != -1 || (c.root_has_x && c.root_has_x[c.creator[k]])) {
         if (c.sp_id) put_hex_id<false>(s, c.sp_id + 32 * k);
         else s.skip(66);
     }
@@ -327,14 +338,17 @@ __global__ void __launch_bounds__(256) k_ev_write(int64_t m, EvCols c, const int
 // The id pass. Workgroup j owns one graph's events of the chunk, grouped by dependency level
 // (LevelPlan); level after level its lanes stride over the level's events: patch the parents' hex ids
 // into the open slots (a parent below `base` from the store's id column, a later one from this
-// chunk's ids), hash the text, store the id. A level's ids are complete before the next level reads
+// chunk's ids; on a context with root ids self-parent -1 from the creator's Root.X row, HGX_ROOT_Y
+// from its Root.Y row and HGX_ROOT_OTHER from the staged op_rid row: level 0, tables written before
+// the launch), hash the text, store the id. A level's ids are complete before the next level reads
 // them: agent-scope fence, barrier, fence; the ids are read past L1. Every lane of the workgroup runs
 // the same wg_nl[j] rounds, and no workgroup waits for another.
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4)))
 k_ev_ids(const int32_t* __restrict__ wg_lo, const int32_t* __restrict__ wg_nl, const int32_t* __restrict__ loff,
          const int32_t* __restrict__ pos, const int64_t* __restrict__ sp, const int64_t* __restrict__ op,
          const int64_t* __restrict__ off, const int64_t* __restrict__ len, const int64_t* __restrict__ slot,
-         int64_t base, const uint8_t* store_id, uint8_t* text, uint8_t* ids) {
+         int64_t base, const uint8_t* store_id, uint8_t* text, uint8_t* ids, const int32_t* __restrict__ creator,
+         RootIds rt, const uint8_t* op_rid) {
     const int32_t lo = wg_lo[blockIdx.x], nl = wg_nl[blockIdx.x];
     for (int32_t l = 0; l < nl; l++) {
         const int32_t a = loff[lo + l], b = loff[lo + l + 1];
@@ -342,15 +356,22 @@ k_ev_ids(const int32_t* __restrict__ wg_lo, const int32_t* __restrict__ wg_nl, c
             const int64_t k = pos[i];
             const int64_t o = off[k], s0 = sp[k], o0 = op[k];
             int64_t at = o + slot[k];
-            if (s0 != -1) {
+            const uint8_t* src = nullptr;
+            if (s0 >= 0) src = s0 < base ? store_id + 32 * s0 : ids + 32 * (s0 - base);
+            else if (rt.has_x && rt.has_x[creator[k]]) src = rt.x_id + 32 * (int64_t)creator[k];
+            if (src) {
                 ByteSink w(text + at);
-                put_hex_id<true>(w, s0 < base ? store_id + 32 * s0 : ids + 32 * (s0 - base));
+                put_hex_id<true>(w, src);
                 w.finish();
                 at += 66;
             }
-            if (o0 != -1) {
+            src = nullptr;
+            if (o0 >= 0) src = o0 < base ? store_id + 32 * o0 : ids + 32 * (o0 - base);
+            else if (o0 == kRootY && rt.y_id) src = rt.y_id + 32 * (int64_t)creator[k];
+            else if (o0 == kRootOther) src = op_rid ? op_rid + 32 * k : nullptr;
+            if (src) {
                 ByteSink w(text + at + 3);
-                put_hex_id<true>(w, o0 < base ? store_id + 32 * o0 : ids + 32 * (o0 - base));
+                put_hex_id<true>(w, src);
                 w.finish();
             }
             sha256_message<false>(text, o, len[k], 0, (uint32_t*)(ids + 32 * k));
@@ -359,6 +380,42 @@ k_ev_ids(const int32_t* __restrict__ wg_lo, const int32_t* __restrict__ wg_nl, c
         __syncthreads();
         __threadfence();
     }
+}
+
+// The value check of Root.Others (hashgraph.go:437-440: Root.Others[event.Hex()] == OtherParent), one
+// lane per chunk event, after the ids are known and before the insert: an HGX_ROOT_OTHER event whose
+// id is no key of the pairs, or whose entry names another other-parent than the supplied one, gets
+// HGX_UNKNOWN_PARENT in the staged column; k_insert_check then rejects it with CheckOtherParent's error
+// at its place in the first-failure order.
+__global__ void __launch_bounds__(256) k_ev_others(int64_t m, int64_t* __restrict__ op, const uint8_t* __restrict__ ids,
+                                                   const uint8_t* __restrict__ op_rid, const uint64_t* __restrict__ pairs,
+                                                   int64_t n_pairs) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= m || op[k] != kRootOther) return;
+    const uint8_t* h = ids + 32 * k;
+    uint64_t q[4];
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        uint64_t x = 0;
+        for (int b = 0; b < 8; b++) x = (x << 8) | h[8 * w + b];
+        q[w] = x;
+    }
+    int64_t lo = 0, hi = n_pairs;
+    while (lo < hi) {   // first key >= q
+        const int64_t mid = (lo + hi) >> 1;
+        const uint64_t* kk = pairs + 8 * mid;
+        int cmp = 0;
+        for (int w = 0; w < 4 && cmp == 0; w++) cmp = kk[w] < q[w] ? -1 : kk[w] > q[w] ? 1 : 0;
+        if (cmp < 0) lo = mid + 1; else hi = mid;
+    }
+    bool ok = op_rid != nullptr && lo < n_pairs;
+    if (ok) {
+        const uint64_t* kk = pairs + 8 * lo;
+        ok = kk[0] == q[0] && kk[1] == q[1] && kk[2] == q[2] && kk[3] == q[3];
+        const uint8_t* v = (const uint8_t*)(kk + 4);
+        for (int b = 0; b < 32 && ok; b++) ok = v[b] == op_rid[32 * k + b];
+    }
+    if (!ok) op[k] = HGX_UNKNOWN_PARENT;
 }
 
 // EventBody.Hash of every event: the body inside the event's text plus '\n'
@@ -407,12 +464,16 @@ struct EvScratch {
     const int32_t *d_wg_lo = nullptr, *d_wg_nl = nullptr, *d_loff = nullptr, *d_pos = nullptr;
     int64_t *d_len = nullptr, *d_off = nullptr, *d_slot = nullptr, *d_blen = nullptr;
     uint8_t *d_ids = nullptr, *d_dig = nullptr;
+    const uint8_t* d_op_rid = nullptr;   // the staged ids of HGX_ROOT_OTHER other-parents, or null
+    int64_t n_root_other = 0;            // the chunk's events with that code (counted when the column is staged)
 
     // Stage events [lo, hi) (m of them): columns, transactions, the parents' ids (json mode) or the
-    // level plan (insert mode, base = gid of event lo) in ONE host-to-device copy.
+    // level plan (insert mode, base = gid of event lo), and on a context with root ids the Root.X flags
+    // and the ids of the HGX_ROOT_OTHER other-parents (op_rid, may be null), in ONE host-to-device copy.
     hipError_t stage(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t lo, int64_t hi, const uint8_t* keys_dev,
                      const uint8_t* keys_host, int32_t n_keys, const uint8_t* sp_id, const uint8_t* op_id, bool with_plan,
-                     int64_t base, int32_t n_per_graph, hipStream_t s) {
+                     int64_t base, int32_t n_per_graph, hipStream_t s, const uint8_t* root_has_x = nullptr,
+                     const uint8_t* op_rid = nullptr) {
         const size_t m = (size_t)(hi - lo);
         const int64_t t0 = txi[(size_t)lo], t1 = txi[(size_t)hi];
         const size_t nt = (size_t)(t1 - t0);
@@ -429,11 +490,11 @@ struct EvScratch {
                                ev.s + 32 * lo, ev.ntx + lo, nullptr, nullptr, nbytes ? ev.tx_bytes + b0 : nullptr,
                                keys_host, sp_id ? sp_id + 32 * lo : nullptr, op_id ? op_id + 32 * lo : nullptr, nullptr,
                                nullptr};
-        size_t bytes[18] = {4 * m, 8 * m, 8 * m, 8 * m, 8 * m, 32 * m, 32 * m, 4 * m, 8 * m, 8 * (nt + 1), nbytes,
+        size_t bytes[19] = {4 * m, 8 * m, 8 * m, 8 * m, 8 * m, 32 * m, 32 * m, 4 * m, 8 * m, 8 * (nt + 1), nbytes,
                             keys_host ? (size_t)65 * (size_t)n_keys : 0, sp_id ? 32 * m : 0, op_id ? 32 * m : 0,
-                            4 * nwg, 4 * nwg, 4 * nloff, with_plan ? 4 * m : 0};
-        size_t o[18], total = 0;
-        for (int i = 0; i < 18; i++) {
+                            4 * nwg, 4 * nwg, 4 * nloff, with_plan ? 4 * m : 0, op_rid ? 32 * m : 0};
+        size_t o[19], total = 0;
+        for (int i = 0; i < 19; i++) {
             o[i] = total;
             total += up256(bytes[i] + 16);   // (16 spare bytes: the hash reader's aligned loads)
         }
@@ -457,6 +518,11 @@ struct EvScratch {
             if (nloff) std::memcpy(h + o[16], plan.loff.data(), 4 * nloff);
             std::memcpy(h + o[17], plan.pos.data(), 4 * m);
         }
+        n_root_other = 0;
+        if (op_rid) {
+            std::memcpy(h + o[18], op_rid + 32 * lo, 32 * m);
+            for (int64_t k = lo; k < hi; k++) n_root_other += ev.op[k] == HGX_ROOT_OTHER;
+        }
         HGX_TRY(hipMemcpyAsync(in.p, h, total, hipMemcpyHostToDevice, s));
         uint8_t* d = in.p;
         cols.creator = (const int32_t*)(d + o[0]); cols.index = (const int64_t*)(d + o[1]);
@@ -465,6 +531,8 @@ struct EvScratch {
         cols.txi = (const int64_t*)(d + o[8]); cols.tx_off = (const int64_t*)(d + o[9]); cols.tx_bytes = d + o[10];
         cols.keys65 = keys_host ? d + o[11] : keys_dev;
         cols.sp_id = sp_id ? d + o[12] : nullptr; cols.op_id = op_id ? d + o[13] : nullptr;
+        cols.root_has_x = root_has_x;
+        d_op_rid = op_rid ? d + o[18] : nullptr;
         d_wg_lo = (const int32_t*)(d + o[14]); d_wg_nl = (const int32_t*)(d + o[15]);
         d_loff = (const int32_t*)(d + o[16]); d_pos = (const int32_t*)(d + o[17]);
         // lengths, offsets (m + 1), slots, body lengths; ids and digests (16-byte aligned)
@@ -498,24 +566,37 @@ void free_ev_scratch(EvScratch* p) { delete p; }
 // chunk, texts -> ids in level order -> body digests -> insert_verified with the chunk's id buffer
 // as the hash column. Stops at the first chunk with a rejected event; out is the last insert's with
 // accepted = the whole call's. Every event of [0, count) has a text (the caller cut the batch).
-hipError_t Engine::insert_bodies(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count, uint8_t* out_id32,
-                                 InsertOut& out) {
+// On a context with root ids (§3.12) the encoder and the id pass read the root tables, op_id32 is staged
+// with each chunk and the Others value check runs before the insert.
+hipError_t Engine::insert_bodies(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count, const uint8_t* op_id32,
+                                 uint8_t* out_id32, InsertOut& out) {
     if (!ev_scratch) ev_scratch = new EvScratch();
     EvScratch& sc = *ev_scratch;
     int64_t done = 0;
     out = InsertOut();
+    RootIds rt{};
+    if (root_ids_set) {
+        const uint8_t* t = root_tab_d.p;
+        rt = RootIds{t, t + 32 * (size_t)C, t + 64 * (size_t)C, t + 65 * (size_t)C, root_pairs_d.p, n_root_pairs};
+    } else {
+        op_id32 = nullptr;
+    }
     if (count <= 0) return insert_verified(InsertIn{}, nullptr, nullptr, 0, out);
     while (done < count) {
         int64_t bound = 0;
         const int64_t hi = bodies_chunk_end(ev, txi, done, count, &bound);
         const int64_t m = hi - done;
-        HGX_TRY(sc.stage(ev, txi, done, hi, pk_keys.p, nullptr, C, nullptr, nullptr, true, E, n, stream));
+        HGX_TRY(sc.stage(ev, txi, done, hi, pk_keys.p, nullptr, C, nullptr, nullptr, true, E, n, stream, rt.has_x, op_id32));
         HGX_TRY(sc.size_and_scan(m, 16, stream));
         HGX_TRY(sc.write(m, (size_t)bound, true, stream));
         const int bs = std::min(1024, std::max(64, (sc.plan.max_width + 63) & ~63));
         hipLaunchKernelGGL(k_ev_ids, dim3((unsigned)sc.plan.wg_lo.size()), dim3(bs), 0, stream, sc.d_wg_lo, sc.d_wg_nl,
                            sc.d_loff, sc.d_pos, sc.cols.sp, sc.cols.op, (const int64_t*)sc.d_off, (const int64_t*)sc.d_len,
-                           (const int64_t*)sc.d_slot, E, (const uint8_t*)g_id.p, sc.text.p, sc.d_ids);
+                           (const int64_t*)sc.d_slot, E, (const uint8_t*)g_id.p, sc.text.p, sc.d_ids, sc.cols.creator, rt,
+                           sc.d_op_rid);
+        if (sc.n_root_other)
+            hipLaunchKernelGGL(k_ev_others, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, m,
+                               const_cast<int64_t*>(sc.cols.op), (const uint8_t*)sc.d_ids, sc.d_op_rid, rt.pairs, rt.n_pairs);
         hipLaunchKernelGGL(k_ev_digest, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, m,
                            (const uint8_t*)sc.text.p, (const int64_t*)sc.d_off, (const int64_t*)sc.d_blen, sc.d_dig);
         HGX_TRY(hipGetLastError());

@@ -259,17 +259,24 @@ class Hashgraph:
             raise e
         return n_ins.value
 
-    def insert_bodies(self, cols: dict, lo: int = 0, hi: Optional[int] = None) -> np.ndarray:
+    def insert_bodies(self, cols: dict, lo: int = 0, hi: Optional[int] = None, other_parent_ids=None) -> np.ndarray:
         """InsertEvent with Event.Hash and Event.Verify computed on the device from the events' fields
         (hgx_insert_event_bodies): events [lo, hi) of body_columns(). Returns the events' ids
         [(hi - lo), 32]. Raises HgxError on the first rejected event, with .inserted = events inserted
-        before it and .ids = their ids."""
+        before it and .ids = their ids. other_parent_ids (hgx_insert_event_bodies_ext): [len(cols), 32]
+        ids, read for the events whose other-parent is ROOT_OTHER on a context with root ids."""
         hi = len(cols["creator"]) if hi is None else hi
         a, ev = _event_bodies_of(cols, lo, hi)
         ids = np.zeros((hi - lo, 32), np.uint8)
         err = hgx_error()
         n_ins = C.c_int64(0)
-        rc = self.L.hgx_insert_event_bodies(self.ctx, C.byref(ev), hi - lo, ptr(ids), C.byref(n_ins), C.byref(err))
+        if other_parent_ids is None:
+            rc = self.L.hgx_insert_event_bodies(self.ctx, C.byref(ev), hi - lo, ptr(ids), C.byref(n_ins), C.byref(err))
+        else:
+            opi = np.ascontiguousarray(np.asarray(other_parent_ids, np.uint8).reshape(-1, 32)[lo:hi])
+            assert opi.shape[0] == hi - lo
+            rc = self.L.hgx_insert_event_bodies_ext(self.ctx, C.byref(ev), ptr(opi), hi - lo, ptr(ids), C.byref(n_ins),
+                                                    C.byref(err))
         if rc:
             e = HgxError(int(err.code or rc), err.msg.decode(errors="replace"))
             e.inserted = n_ins.value
@@ -519,6 +526,25 @@ class Hashgraph:
         if others is not None and len(others):
             k = np.ascontiguousarray(others, np.uint8).reshape(-1, 32)
             self._call(lambda ctx, e: self.L.hgx_set_root_others(ctx, ptr(k), k.shape[0], e))
+
+    def SetRootIds(self, x, y, others=()):
+        """The ids of the roots installed by Reset (hgx_set_root_ids): x[p] / y[p] = the 32-byte id of
+        participant p's Root.X / Root.Y (None for ""), others = (event id, other-parent id) pairs of
+        the roots' Others maps. Afterwards GetRootIds / GetRootOthers answer and insert_bodies works."""
+        C_ = self.n * self.G
+        cols = []
+        for v in (x, y):
+            has = np.asarray([0 if b is None else 1 for b in v], np.int32)
+            ids = np.zeros((C_, 32), np.uint8)
+            for p, b in enumerate(v):
+                if b is not None:
+                    ids[p] = np.frombuffer(bytes(b), np.uint8)
+            cols += [ids, has]
+        others = list(others)
+        ke = np.frombuffer(b"".join(bytes(k) for k, _ in others) + bytes(32), np.uint8)
+        kv = np.frombuffer(b"".join(bytes(v) for _, v in others) + bytes(32), np.uint8)
+        self._call(lambda ctx, e: self.L.hgx_set_root_ids(ctx, ptr(cols[0]), ptr(cols[1]), ptr(cols[2]), ptr(cols[3]),
+                                                          ptr(ke), ptr(kv), len(others), e))
 
     def GetFrame(self):
         """Hashgraph.GetFrame (hashgraph.go:897-995): roots (x, y, index, round per participant),

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define HGX_ABI_VERSION 6   /* (still 6 with hgx_insert_event_bodies, hgx_event_json_batch and hgx_batch_levels,
+#define HGX_ABI_VERSION 6   /* (still 6 with hgx_insert_event_bodies(_ext), hgx_set_root_ids, hgx_event_json_batch and hgx_batch_levels,
                                  and with hgx_prune_to_frame, hgx_get_root_ids and hgx_get_root_others:
                                  purely additive, no existing entry or structure changed)
                               6: hgx_host_alloc / hgx_host_free (page-locked caller buffers);
@@ -67,7 +67,8 @@ enum {
  * creator's Root (hashgraph.go:430-440): */
 #define HGX_ROOT_Y (-3)       /* Root.Y (the creator's first event, self-parent = Root.X = -1) */
 #define HGX_ROOT_OTHER (-4)   /* Root.Others[event]: the event's hash must be a key registered with
-                                 hgx_set_root_others (the caller checked the entry's value) */
+                                 hgx_set_root_others (the caller checked the entry's value; on the
+                                 body path, hgx_insert_event_bodies_ext, the device checks it) */
 
 typedef struct {
     int32_t code;
@@ -235,7 +236,8 @@ typedef struct {
  * hgx_get_event_id works afterwards. Needs hgx_set_participant_keys. HGX_ERR_INVALID "<reason>":
  * bad columns (a NULL column, ntx < -1, decreasing tx_off: checked before anything else), keys not
  * set, the context's ids are not known (events came through hgx_events32 / packed inserts or an
- * id-less bootstrap), the context is in use after hgx_reset, or it is chain-sharded or row-sharded.
+ * id-less bootstrap), the context has roots whose ids are not known (after hgx_reset with roots or a
+ * rooted hgx_bootstrap, until hgx_set_root_ids), or it is chain-sharded or row-sharded.
  * Deviation from the reference: an event whose creator has no key, or with a parent that is neither
  * -1 nor an earlier gid (HGX_UNKNOWN_PARENT included), has no id string, so no text. The batch is
  * cut before it, the prefix is inserted first (its first failure wins), then the event fails with
@@ -247,9 +249,28 @@ typedef struct {
  * whatever the batch size: on the device 32 MiB of text, at most 24 MiB of transaction bytes and 32 MiB
  * of their offsets, and 220 bytes per event of a chunk for columns, level plan, ids and digests (under
  * 104 MiB in all); the same without the text in page-locked host memory. Only a single event whose
- * own text exceeds 32 MiB raises it, to that event's size. */
+ * own text exceeds 32 MiB raises it, to that event's size. With other_parent_id32 (_ext) 32 bytes more
+ * per event of a chunk on both sides: 252 bytes per event, under 106 MiB in all.
+ * hgx_insert_event_bodies is hgx_insert_event_bodies_ext with other_parent_id32 = NULL. */
 int32_t hgx_insert_event_bodies(hgx_ctx* ctx, const hgx_event_bodies* ev, int64_t count, uint8_t* out_id32,
                                 int64_t* n_inserted, hgx_error* err);
+/* The same on a context with roots (after hgx_prune_to_frame, or hgx_reset + hgx_set_root_ids;
+ * DESIGN.md §3.12), where an event's Body.Parents may name events outside the store (hashgraph.go:404-445).
+ * The parent codes print as
+ *   self-parent -1   the creator's Root.X id, or "" where the root has none (has_x = 0);
+ *   HGX_ROOT_Y       the creator's Root.Y id;
+ *   HGX_ROOT_OTHER   that event's row of other_parent_id32 (32 bytes per event, host memory, read only
+ *                    for this code; may be NULL);
+ *   a gid            as above.
+ * An HGX_ROOT_Y event whose creator's root has no Y, an HGX_ROOT_OTHER event without other_parent_id32
+ * and any other negative code have no text: the batch is cut before them by the deviation rule above.
+ * The device checks the Root.Others entry of every HGX_ROOT_OTHER event after its id is known: the id
+ * must be a key of the roots' pairs (hgx_get_root_others) and the entry must equal the supplied id,
+ * else the event fails with "CheckOtherParent: Other-parent not known" at its position (after "Invalid
+ * signature" at the same event). On a context without roots the call equals hgx_insert_event_bodies
+ * byte for byte. */
+int32_t hgx_insert_event_bodies_ext(hgx_ctx* ctx, const hgx_event_bodies* ev, const uint8_t* other_parent_id32,
+                                    int64_t count, uint8_t* out_id32, int64_t* n_inserted, hgx_error* err);
 /* The encoder alone: Event.Marshal bytes (json.Encoder output of {Body, R, S}, event.go:155-162) of
  * a batch whose parents' ids the caller supplies (sp_id32 / op_id32: 32 bytes per event, ignored
  * where the parent gid is -1; a parent is printed when its gid is not -1). keys65: n_keys keys of 65
@@ -413,12 +434,27 @@ int32_t hgx_prune_to_frame(hgx_ctx* ctx, int64_t* old_gid, int64_t cap, int64_t*
  * roots' Others pairs (event id, other-parent id), sorted by event id; *count in full, the arrays
  * get the first `cap`. hgx_prune_to_frame gathers them before the dropped events go, and carries
  * them over a further prune (a participant without events keeps its whole root). Known only while
- * every root traces back to genesis through prunes: after the caller's own hgx_reset with roots,
- * or a rooted hgx_bootstrap, both return HGX_ERR_INVALID "root ids not known". */
+ * every root traces back to genesis through prunes, or the caller installed them: after the caller's
+ * own hgx_reset with roots, or a rooted hgx_bootstrap, both return HGX_ERR_INVALID "root ids not
+ * known" until hgx_set_root_ids. */
 int32_t hgx_get_root_ids(hgx_ctx* ctx, int32_t participant, uint8_t* x_id32, int32_t* has_x, uint8_t* y_id32,
                          int32_t* has_y, hgx_error* err);
 int32_t hgx_get_root_others(hgx_ctx* ctx, uint8_t* event_id32, uint8_t* other_parent_id32, int64_t cap,
                             int64_t* count, hgx_error* err);
+/* The ids of roots the caller installed with hgx_reset (a fast-forward join: Reset(frame.Roots),
+ * hashgraph.go:877-895): per participant Root.X (x_id32, has_x: 0 for "") and Root.Y (y_id32, has_y),
+ * 32 bytes per participant (rows with has = 0 are not read; a column may be NULL when every flag is 0),
+ * and the Others pairs (event id, other-parent id), n_others of them in any order. The library sorts
+ * the pairs by event id; their keys replace those of hgx_set_root_others. Afterwards the root ids are
+ * known: hgx_get_root_ids / hgx_get_root_others answer, hgx_insert_event_bodies_ext works, and a later
+ * hgx_prune_to_frame carries the ids on. A copy of the tables lives on the device (66 bytes per
+ * participant and 64 per pair). HGX_ERR_INVALID "<reason>", with nothing changed: ctx NULL, a batch
+ * (G > 1), chain-sharded or row-sharded context, has_y[p] different from the root's root_y_is_event,
+ * an event id twice in the pairs, pairs on a context without roots, or events already resident (call
+ * it between hgx_reset and the first insert). */
+int32_t hgx_set_root_ids(hgx_ctx* ctx, const uint8_t* x_id32, const int32_t* has_x, const uint8_t* y_id32,
+                         const int32_t* has_y, const uint8_t* others_event_id32, const uint8_t* others_parent_id32,
+                         int64_t n_others, hgx_error* err);
 
 /* ---- Hashgraph state (hashgraph.go:15-37) --------------------------------- */
 int64_t hgx_num_events(hgx_ctx* ctx);

@@ -101,6 +101,19 @@ int main() {
             CHECK(hgx::bodies_first_unencodable(ev, count, base, n * graphs) == k);
             op[(size_t)k] = HGX_UNKNOWN_PARENT;
             CHECK(hgx::bodies_first_unencodable(ev, count, base, n * graphs) == k);
+            // the root codes have a text on a context with root ids only
+            std::vector<uint8_t> has_y((size_t)(n * graphs), 0);
+            op[(size_t)k] = HGX_ROOT_Y;
+            CHECK(hgx::bodies_first_unencodable(ev, count, base, n * graphs) == k);
+            CHECK(hgx::bodies_first_unencodable(ev, count, base, n * graphs, has_y.data(), true) == k);
+            has_y[(size_t)creator[(size_t)k]] = 1;
+            CHECK(hgx::bodies_first_unencodable(ev, count, base, n * graphs, has_y.data(), false) == count);
+            op[(size_t)k] = HGX_ROOT_OTHER;
+            CHECK(hgx::bodies_first_unencodable(ev, count, base, n * graphs, has_y.data(), false) == k);
+            CHECK(hgx::bodies_first_unencodable(ev, count, base, n * graphs, has_y.data(), true) == count);
+            CHECK(hgx_batch_levels(sp.data(), op.data(), count, base, level.data(), &nl, &err) == HGX_OK);
+            op[(size_t)k] = -5;
+            CHECK(hgx::bodies_first_unencodable(ev, count, base, n * graphs, has_y.data(), true) == k);
             op[(size_t)k] = keep;
             if (tx_off.size() > 2) {
                 tx_off[1] += 1000000000;
