@@ -59,6 +59,18 @@ class hgx_wire_events(C.Structure):
                  "timestamp_ns", "hash", "sig_s", "ntx", "tx_nil")]
 
 
+# hgx_wire_out's columns in declaration order with their numpy dtypes and row shapes
+WIRE_OUT_COLUMNS = (("gid", np.int64, ()), ("creator_id", np.int32, ()), ("index", np.int64, ()),
+                    ("self_parent_index", np.int64, ()), ("other_parent_creator", np.int32, ()),
+                    ("other_parent_index", np.int64, ()), ("timestamp_ns", np.int64, ()), ("hash", np.uint8, (32,)),
+                    ("sig_s", np.uint8, (32,)), ("ntx", np.int32, ()), ("tx_nil", np.int32, ()),
+                    ("root_parent", np.uint8, ()))
+
+
+class hgx_wire_out(C.Structure):
+    _fields_ = [(nm, C.c_void_p) for nm, _, _ in WIRE_OUT_COLUMNS]
+
+
 def ptr(a: np.ndarray):
     assert a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(C.c_void_p)
@@ -167,6 +179,7 @@ def lib():
     _sig(L, "hgx_get_event", i32, [p, i64, p, p, p, p, p, p, p, E])
     _sig(L, "hgx_wire_info", i32, [p, i64, i64, p, p, p])
     _sig(L, "hgx_read_wire_info", i32, [p, i32, i64, i32, i64, p, p, E])
+    _sig(L, "hgx_diff_wire", i32, [p, i32, p, i64, p, i64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), E])
     _sig(L, "hgx_get_rounds", i32, [p, i64, i64, p, p, p])
     _sig(L, "hgx_get_received", i32, [p, i64, i64, p, p])
     _sig(L, "hgx_get_coords", i32, [p, i64, p, p])

@@ -21,6 +21,7 @@
 
 #include "hgx.h"
 #include "hgx_bodies.h"
+#include "hgx_diff.h"
 #include "hgx_engine.h"
 
 namespace {
@@ -2498,6 +2499,51 @@ int32_t hgx_wire_info(hgx_ctx* c, int64_t first, int64_t count, int32_t* self_pa
         if (other_parent_index) other_parent_index[k] = op >= 0 ? c->index32[(size_t)op] : -1;
     }
     return HGX_OK;
+}
+
+// node.processSyncRequest's Core.OverSyncLimit, Core.Diff and ToWire (node/node.go:214-270,
+// node/core.go:147-188) in one call: the host plan sizes the answer from the per-chain mirrors, the
+// device filters and gathers where the events live. The host mirror of the event
+// columns is neither read nor dropped.
+int32_t hgx_diff_wire(hgx_ctx* c, int32_t g, const int32_t* known, int64_t sync_limit, hgx_wire_out* out, int64_t cap,
+                      int64_t* count, int32_t* over_limit, hgx_error* err) {
+    auto invalid = [&](const char* why) {
+        set_err(err, HGX_ERR_INVALID, std::string("hgx_diff_wire: ") + why);
+        return HGX_ERR_INVALID;
+    };
+    if (!c || !known || !out || !count) return invalid("bad arguments");
+    if (g < 0 || g >= c->G) return invalid("bad graph");
+    if (cap < 0) return invalid("negative cap");
+    if (c->grp) return invalid("not available on a chain-sharded context");
+    if (out->hash && !c->eng.ids_known) return invalid("the context's event ids are not known");
+    const size_t c0 = (size_t)g * (size_t)c->n;
+    hgx::DiffPlan plan;
+    hgx::diff_plan(known, c->last_index.data() + c0, c->chain_len.data() + c0, c->n, sync_limit, plan);
+    if (plan.over_limit) {
+        *count = plan.unknown;
+        if (over_limit) *over_limit = 1;
+        return ok(err);
+    }
+    if (plan.fail >= 0) {
+        set_err(err, HGX_ERR_TOO_LATE, plan.msg);
+        return HGX_ERR_TOO_LATE;
+    }
+    DeviceGuard dg(c);
+    const hgx::Engine::DiffCols cols{out->gid, out->index, out->self_parent_index, out->other_parent_index,
+                                     out->timestamp_ns, out->creator_id, out->other_parent_creator, out->ntx,
+                                     out->tx_nil, out->hash, out->sig_s, out->root_parent};
+    int64_t dev_total = 0;
+    const hipError_t e = c->eng.diff_wire(g, known, c->root_index.data() + c0, std::min(cap, plan.total), plan.total,
+                                          cols, &dev_total);
+    if (e != hipSuccess) return dev_err(err, e, "hgx_diff_wire");
+    if (dev_total != plan.total) {
+        set_err(err, HGX_ERR_PANIC, "hgx_diff_wire: the device selected " + std::to_string(dev_total) +
+                                        " events, the host plan " + std::to_string(plan.total));
+        return HGX_ERR_PANIC;
+    }
+    *count = plan.total;
+    if (over_limit) *over_limit = 0;
+    return ok(err);
 }
 
 // ReadWireInfo (hashgraph.go:569-614): the parents of a wire event resolved through

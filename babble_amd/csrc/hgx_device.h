@@ -9,6 +9,25 @@ namespace hgx {
 
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
+// exclusive scan of one value per thread over a block of 256 threads (sh: 4 words of LDS); *total =
+// the block's sum. Every thread of the block must call it.
+__device__ __forceinline__ uint32_t block_excl_scan256(uint32_t v, uint32_t* sh, uint32_t* total) {
+    // 256 threads: wave-level inclusive scan by shuffles, then wave totals
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    uint32_t x = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(x, o);
+        if (lane >= o) x += y;
+    }
+    if (lane == 63) sh[wave] = x;
+    __syncthreads();
+    uint32_t wbase = 0;
+    for (int w = 0; w < wave; w++) wbase += sh[w];
+    *total = sh[0] + sh[1] + sh[2] + sh[3];
+    __syncthreads();
+    return wbase + x - v;
+}
+
 // Strongly-see count of 8-bit rebased coordinates, 4 per dword: window bytes hold LA' in [0, 126], the
 // candidate's bytes nf = 128 - FD' with FD' in [1, 127] (127 = none), so LA' + nf lies in [1, 253]: no
 // carry leaves a byte, and bit 7 is set exactly when LA' >= FD'. With no carries the add may span 64

@@ -137,6 +137,7 @@ Engine::~Engine() {
     if (h_cpar) (void)hipHostFree(h_cpar);
     if (h_flag) (void)hipHostFree(h_flag);
     if (h_segc) (void)hipHostFree(h_segc);
+    if (df_host) (void)hipHostFree(df_host);
     if (stream_o) (void)hipStreamSynchronize(stream_o);
     for (auto e : ev_o)
         if (e) (void)hipEventDestroy(e);
@@ -943,6 +944,86 @@ hipError_t Engine::prune_to_frame(const std::vector<int32_t>& root_round, const 
     HGX_TRY(set_roots(root_round, y_ext));
     HGX_TRY(set_root_others(st.oth_key.data(), st.n_others));
     return insert(pr_in, count, out);
+}
+
+// ---- hgx_diff_wire (hgx_diff.hip) -----------------------------------------
+// The host plan gave the exact row count, so the staging and the read-back are sized before any
+// launch: known | root_index go up through the staged-copy path, three launches, and the header
+// (the device's total) with every requested column comes back in ONE copy, then one synchronise.
+hipError_t Engine::diff_wire(int graph, const int32_t* known, const int32_t* root_index, int64_t rows, int64_t expect,
+                             const DiffCols& out, int64_t* dev_total) {
+    *dev_total = expect;
+    if (graph < 0 || graph >= G || rows < 0 || rows > expect || expect > E || (out.hash && !ids_known))
+        return hipErrorInvalidValue;
+    if (rows == 0) return hipSuccess;   // a sizing call: the plan's total is the answer, nothing to launch
+    // a payload copy of a split insert still in flight: the gather reads g_S (g_ts / g_id were joined
+    // by payload_end, which every split insert runs before it returns)
+    HGX_TRY(payload_wait_S());
+    const size_t R = (size_t)rows, nb = (size_t)((E + kDiffChunk - 1) / kDiffChunk), nz = (size_t)n;
+    size_t total = 0;
+    auto take = [&](size_t bytes) {
+        const size_t off = total;
+        total += (bytes + 255) & ~(size_t)255;
+        return off;
+    };
+    const size_t o_tab = take(2 * nz * 4), o_part = take(nb * 4), o_hdr = take(256);
+    // the columns, widest first so that each stays aligned to its element (the 32-byte rows to 16)
+    size_t col = o_hdr + 256;
+    auto column = [&](const void* want, size_t width) {
+        if (!want) return (size_t)0;
+        const size_t off = col;
+        col += width * R;
+        return off;
+    };
+    const size_t c_hash = column(out.hash, 32), c_S = column(out.S, 32), c_gid = column(out.gid, 8),
+                 c_index = column(out.index, 8), c_spi = column(out.spi, 8), c_opi = column(out.opi, 8),
+                 c_ts = column(out.ts, 8), c_creator = column(out.creator, 4), c_opc = column(out.opc, 4),
+                 c_ntx = column(out.ntx, 4), c_nil = column(out.nil, 4), c_root = column(out.root, 1);
+    total = col;
+    if (df_buf.n < total) HGX_TRY(df_buf.alloc(std::max(total, 2 * df_buf.n)));
+    const size_t back = col - o_hdr;   // header + columns
+    if (df_host_cap < back) {
+        if (df_host) (void)hipHostFree(df_host);
+        df_host = nullptr;
+        df_host_cap = 0;
+        const size_t want = std::max(back, (size_t)1 << 16);
+        HGX_TRY(hipHostMalloc((void**)&df_host, want, hipHostMallocDefault));
+        df_host_cap = want;
+    }
+    uint8_t* b = df_buf.p;
+    DiffArgs a{};
+    a.E = E; a.rows = rows; a.c0 = graph * n; a.n = n;
+    a.g_creator = g_creator.p; a.g_index = g_index.p; a.g_sp = g_sp.p; a.g_op = g_op.p; a.g_ntx = g_ntx.p;
+    a.g_ts = g_ts.p; a.g_S = g_S.p; a.g_id = g_id.p; a.g_txnil = g_txnil.p;
+    a.tab = (const int32_t*)(b + o_tab); a.part = (uint32_t*)(b + o_part); a.total = (uint32_t*)(b + o_hdr);
+    auto at = [&](size_t off) { return off ? b + off : nullptr; };
+    a.o_hash = at(c_hash); a.o_S = at(c_S);
+    a.o_gid = (int64_t*)at(c_gid); a.o_index = (int64_t*)at(c_index); a.o_spi = (int64_t*)at(c_spi);
+    a.o_opi = (int64_t*)at(c_opi); a.o_ts = (int64_t*)at(c_ts);
+    a.o_creator = (int32_t*)at(c_creator); a.o_opc = (int32_t*)at(c_opc); a.o_ntx = (int32_t*)at(c_ntx);
+    a.o_nil = (int32_t*)at(c_nil); a.o_root = at(c_root);
+    std::vector<int32_t> tab(2 * nz);
+    std::memcpy(tab.data(), known, nz * 4);
+    std::memcpy(tab.data() + nz, root_index, nz * 4);
+    HGX_TRY(stage_h2d(b + o_tab, tab.data(), 2 * nz * 4));
+    HGX_TRY(stage_issue());
+    launch_diff(stream, a);
+    HGX_TRY(hipGetLastError());
+    HGX_TRY(hipMemcpyAsync(df_host, b + o_hdr, back, hipMemcpyDeviceToHost, stream));
+    HGX_TRY(hipStreamSynchronize(stream));
+    stage_flush();
+    uint32_t dt = 0;
+    std::memcpy(&dt, df_host, 4);
+    *dev_total = dt;
+    if ((int64_t)dt == expect) {   // (a mismatch is a bug the caller reports: nothing is handed out)
+        auto give = [&](void* dst, size_t off, size_t width) {
+            if (dst && off) std::memcpy(dst, df_host + (off - o_hdr), width * R);
+        };
+        give(out.hash, c_hash, 32); give(out.S, c_S, 32); give(out.gid, c_gid, 8); give(out.index, c_index, 8);
+        give(out.spi, c_spi, 8); give(out.opi, c_opi, 8); give(out.ts, c_ts, 8); give(out.creator, c_creator, 4);
+        give(out.opc, c_opc, 4); give(out.ntx, c_ntx, 4); give(out.nil, c_nil, 4); give(out.root, c_root, 1);
+    }
+    return hipSuccess;
 }
 
 hipError_t Engine::get_ids(int64_t first, int64_t count, uint8_t* out32) {

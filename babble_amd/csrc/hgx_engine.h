@@ -220,6 +220,18 @@ class Engine {
     hipError_t prune_stage(const std::vector<int32_t>& cut, int64_t n_kept, PruneOut& out);
     hipError_t prune_to_frame(const std::vector<int32_t>& root_round, const std::vector<uint8_t>& y_ext,
                               const PruneOut& st, InsertOut& out);
+    // hgx_diff_wire (hgx_diff.hip): graph `graph`'s events with Index > known[creator]
+    // in gid order, as wire columns (host pointers, null = not wanted; `rows` entries each are
+    // filled, rows <= expect = the host plan's total; rows = 0 launches nothing). known / root_index:
+    // n entries. *dev_total = the device's own count: unless it equals expect (a bug the caller
+    // reports) no column is written. Changes nothing but scratch.
+    struct DiffCols {
+        int64_t *gid, *index, *spi, *opi, *ts;
+        int32_t *creator, *opc, *ntx, *nil;
+        uint8_t *hash, *S, *root;
+    };
+    hipError_t diff_wire(int graph, const int32_t* known, const int32_t* root_index, int64_t rows, int64_t expect,
+                         const DiffCols& out, int64_t* dev_total);
     // chain lengths at the last DivideRounds (events past them have no round yet)
     int32_t len_div(int chain) const { return laid_out && chain < (int)h_len_div.size() ? h_len_div[(size_t)chain] : 0; }
     // per-event columns (gid order) for the host-side getters
@@ -385,6 +397,12 @@ class Engine {
     DBuf<uint8_t> pr_buf;
     InsertIn pr_in{};
     int64_t pr_count = -1;   // events staged by prune_stage (-1: none)
+    // hgx_diff_wire: known | root_index, the per-2 048-gid partials, then a 256-byte header (the
+    // device's total) and the output columns, 121 bytes per returned row; the header and the
+    // columns come back in one copy into df_host (page-locked). Both grown on demand.
+    DBuf<uint8_t> df_buf;
+    uint8_t* df_host = nullptr;
+    size_t df_host_cap = 0;
     // batches of at most kPackEvents from host memory: the columns packed in one pinned buffer,
     // one H2D copy into st_pack
     static constexpr int64_t kPackEvents = 65536;

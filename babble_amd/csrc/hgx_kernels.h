@@ -371,4 +371,26 @@ struct PruneArgs {
 };
 void launch_prune(hipStream_t s, const PruneArgs& a, uint32_t* scan_part);
 
+// the scan's middle step alone: exclusive scan of nparts block totals in place (k_scan_top)
+void launch_scan_top(hipStream_t s, uint32_t* part, int nparts);
+
+// hgx_diff_wire (hgx_diff.hip): the events of graph creators [c0, c0 + n) with Index >
+// known[creator - c0], in gid order, as the columns of hgx_wire_out. A null output column is skipped.
+struct DiffArgs {
+    int64_t E;                 // resident events
+    int64_t rows;              // min(cap, the host plan's total): rows at or beyond are not written
+    int c0, n;
+    const int32_t *g_creator, *g_index, *g_sp, *g_op, *g_ntx;
+    const int64_t* g_ts;
+    const uint8_t *g_S, *g_id, *g_txnil;
+    const int32_t* tab;        // known[n] | root_index[n]
+    uint32_t* part;            // [blocks] selected events per 2 048 gids, then their exclusive scan
+    uint32_t* total;           // the device's count (the last workgroup writes it)
+    int64_t *o_gid, *o_index, *o_spi, *o_opi, *o_ts;
+    int32_t *o_creator, *o_opc, *o_ntx, *o_nil;
+    uint8_t *o_hash, *o_S, *o_root;
+};
+constexpr int kDiffChunk = 2048;   // gids per workgroup (= k_scan_top's partials)
+void launch_diff(hipStream_t s, const DiffArgs& a);
+
 }  // namespace hgx

@@ -1466,24 +1466,7 @@ __global__ void __launch_bounds__(kSortThreads) k_radix_hist(const uint64_t* __r
 
 // exclusive scan of `total` u32 in place: per-2048 chunk sums, scan of the sums in
 // one block, then per-chunk rescan with the chunk offset.
-constexpr int kScanChunk = 2048;
-
-__device__ __forceinline__ uint32_t block_excl_scan256(uint32_t v, uint32_t* sh, uint32_t* total) {
-    // 256 threads: wave-level inclusive scan by shuffles, then wave totals
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    uint32_t x = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) sh[wave] = x;
-    __syncthreads();
-    uint32_t wbase = 0;
-    for (int w = 0; w < wave; w++) wbase += sh[w];
-    *total = sh[0] + sh[1] + sh[2] + sh[3];
-    __syncthreads();
-    return wbase + x - v;
-}
+constexpr int kScanChunk = 2048;   // (block_excl_scan256: hgx_device.h)
 
 __global__ void __launch_bounds__(256) k_scan_reduce(const uint32_t* __restrict__ a, int64_t total,
                                                      uint32_t* __restrict__ part) {
@@ -2541,6 +2524,10 @@ void launch_scan_u32(hipStream_t s, uint32_t* buf, int64_t total, uint32_t* part
     hipLaunchKernelGGL(k_scan_reduce, dim3(nparts), dim3(256), 0, s, buf, total, part);
     hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, s, part, nparts);
     hipLaunchKernelGGL(k_scan_down, dim3(nparts), dim3(256), 0, s, buf, total, part);
+}
+
+void launch_scan_top(hipStream_t s, uint32_t* part, int nparts) {
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, s, part, nparts);
 }
 
 static void scan_u32(hipStream_t s, const DevArrays& a, uint32_t* buf, int64_t total) {

@@ -739,6 +739,46 @@ class Hashgraph:
                 raise HgxError(rc, "hgx_wire_info failed")
         return a[:count], b[:count], c[:count]
 
+    def DiffWire(self, known, sync_limit: int = -1, graph: int = 0, cap: Optional[int] = None, columns=None):
+        """node.processSyncRequest's OverSyncLimit + Diff + ToWire in one call on the device
+        (hgx_diff_wire): the events the peer's `known` vector lacks, in topological order, as the wire
+        columns insert_wire takes. Returns (cols, count, over_limit): cols maps hgx_wire_out's column
+        names to arrays of min(cap, count) rows (empty when over the limit). cap=None sizes by the count
+        (one sizing call with cap=0); columns = the names to request (default: all, without "hash"
+        when the context's event ids are not known, which a sizing call with "hash" finds out)."""
+        known = np.ascontiguousarray(known, np.int32)
+        if known.shape != (self.n,):
+            raise ValueError(f"known must have {self.n} entries")
+        spec = {nm: (dt, shp) for nm, dt, shp in _lib.WIRE_OUT_COLUMNS}
+        want = list(spec) if columns is None else list(columns)
+        bad = [nm for nm in want if nm not in spec]
+        if bad:
+            raise ValueError(f"unknown columns {bad}")
+        cnt, over = C.c_int64(0), C.c_int32(0)
+
+        def call(cols, rows):
+            out, err = _lib.hgx_wire_out(**{nm: ptr(a) for nm, a in cols.items()}), hgx_error()
+            rc = self.L.hgx_diff_wire(self.ctx, graph, ptr(known), sync_limit, C.byref(out), rows, C.byref(cnt),
+                                      C.byref(over), C.byref(err))
+            return rc, err
+
+        def alloc(rows):
+            return {nm: np.zeros((max(rows, 1),) + spec[nm][1], spec[nm][0]) for nm in want}
+
+        if cap is None or columns is None:   # the sizing call: the count, and whether "hash" can be had
+            rc, err = call(alloc(0), 0)
+            if rc == 102 and columns is None and b"ids are not known" in err.msg:
+                want.remove("hash")
+                rc, err = call(alloc(0), 0)
+            _lib.check(rc, err)
+        rows = cnt.value if cap is None else int(cap)
+        cols = alloc(rows)
+        if not (over.value and cap is None):
+            rc, err = call(cols, rows)
+            _lib.check(rc, err)
+        m = 0 if over.value else min(rows, cnt.value)
+        return {nm: a[:m] for nm, a in cols.items()}, cnt.value, bool(over.value)
+
     def ReadWireInfo(self, creator: int, sp_index: int, op_creator: int, op_index: int):
         sp, op, err = C.c_int64(), C.c_int64(), hgx_error()
         _lib.check(self.L.hgx_read_wire_info(self.ctx, creator, sp_index, op_creator, op_index, C.byref(sp),

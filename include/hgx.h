@@ -37,7 +37,7 @@ extern "C" {
 #endif
 
 #define HGX_ABI_VERSION 6   /* (still 6 with hgx_insert_event_bodies(_ext), hgx_set_root_ids, hgx_event_json_batch and hgx_batch_levels,
-                                 and with hgx_prune_to_frame, hgx_get_root_ids and hgx_get_root_others:
+                                 with hgx_prune_to_frame, hgx_get_root_ids and hgx_get_root_others, and with hgx_diff_wire:
                                  purely additive, no existing entry or structure changed)
                               6: hgx_host_alloc / hgx_host_free (page-locked caller buffers);
                               5: hgx_events_packed (hgx_insert_events_packed, hgx_insert_and_run_packed,
@@ -521,6 +521,54 @@ int32_t hgx_wire_info(hgx_ctx* ctx, int64_t first, int64_t count, int32_t* self_
  * through ParticipantEvent (its errors) */
 int32_t hgx_read_wire_info(hgx_ctx* ctx, int32_t creator, int64_t self_parent_index, int32_t other_parent_creator,
                            int64_t other_parent_index, int64_t* self_parent, int64_t* other_parent, hgx_error* err);
+
+/* ---- answering a SyncRequest (node/node.go:214-270) ------------------------
+ * SyncResponse.Events as columns: the writable twin of hgx_wire_events plus the sender's gid.
+ * Caller-allocated, `cap` entries each; a NULL column is skipped. */
+typedef struct {
+    int64_t* gid;                   /* the sender's gid (its body store's key) */
+    int32_t* creator_id;            /* WireBody.CreatorID */
+    int64_t* index;                 /* WireBody.Index */
+    int64_t* self_parent_index;     /* WireBody.SelfParentIndex (Root.Index for a chain's first event) */
+    int32_t* other_parent_creator;  /* WireBody.OtherParentCreatorID (-1: "") */
+    int64_t* other_parent_index;    /* WireBody.OtherParentIndex (-1: "") */
+    int64_t* timestamp_ns;
+    uint8_t* hash;                  /* 32 B per event: Event.Hash; needs the context's ids */
+    uint8_t* sig_s;                 /* 32 B per event */
+    int32_t* ntx;
+    int32_t* tx_nil;
+    uint8_t* root_parent;           /* 0, or 1 / 2: the other-parent was inserted as HGX_ROOT_Y / HGX_ROOT_OTHER */
+} hgx_wire_out;
+/* node.processSyncRequest's three steps in one call, where the events live. known:
+ * the peer's Hashgraph.Known(), one entry per participant of `graph` (the last Index it has, -1 none).
+ *  1. Core.OverSyncLimit (node/core.go:147-159), on the host: sum over i of max(0, last_index[i] -
+ *     known[i]). If sync_limit >= 0 and the sum exceeds it: *over_limit = 1, *count = the sum, nothing
+ *     else written, HGX_OK. sync_limit < 0: no limit.
+ *  2. Core.Diff (node/core.go:166-188): Store.ParticipantEvents(pk, known[id]) per participant, with
+ *     the window rule and errors of hgx_participant_events: nothing when known > last, HGX_ERR_TOO_LATE
+ *     "\x03, Too Late" when known + 1 < the oldest Index (common/rolling_index.go:21-39). The
+ *     participants are checked in ascending id and the first failing one is reported; Go ranges over
+ *     a map, so with two failing participants the reference's choice is random. An error leaves every
+ *     output untouched.
+ *  3. The selected events in ascending gid (ByTopologicalOrder), each as ToWire gives it
+ *     (hashgraph.go:532-567): self_parent_index = the self-parent's Index, or the creator's Root.Index
+ *     where the stored self-parent is -1; other_parent_creator / other_parent_index from the stored
+ *     other-parent gid, -1 / -1 when there is none. An other-parent stored as a root code (after
+ *     hgx_reset or hgx_prune_to_frame) has no wire index in libhgx: the row reports the code in
+ *     root_parent and -1 / -1 in the two columns, as hgx_wire_info does, and the caller fills them from
+ *     its own store.
+ * *count = the full number of events; the arrays get the first min(cap, *count) rows and rows beyond
+ * that are not written; *over_limit = 0 (over_limit may be NULL). creator_id and other_parent_creator
+ * are ids within the graph, 0..n-1, as a WireBody carries them, so the columns are directly the
+ * hgx_wire_events of hgx_insert_wire_events on the peer. R and the transaction bytes stay with the
+ * caller's body store, keyed by gid. Works on batched (G > 1) and row-sharded contexts. The call
+ * changes no context state apart from scratch buffers (121 bytes per returned row, and one word per
+ * 2 048 resident events), and neither builds nor drops the host mirror behind the other store views.
+ * HGX_ERR_INVALID "<reason>", nothing written: NULL ctx, known, out or count; graph outside the
+ * context; cap < 0; a chain-sharded context; out->hash on a context whose event ids are not known
+ * (hgx_events32 / packed inserts: the other columns still work there). */
+int32_t hgx_diff_wire(hgx_ctx* ctx, int32_t graph, const int32_t* known, int64_t sync_limit,
+                      hgx_wire_out* out, int64_t cap, int64_t* count, int32_t* over_limit, hgx_error* err);
 
 /* ---- per-event results (bulk) --------------------------------------------- */
 /* round (Round), witness (Witness), famous (RoundEvent.Famous: 0 Undefined,1 True,2 False) */
