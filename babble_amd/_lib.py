@@ -208,6 +208,7 @@ def lib():
     _sig(L, "hgx_set_cts_kernel", i32, [p, i32])
     _sig(L, "hgx_set_root_others", i32, [p, p, i64, p])
     _sig(L, "hgx_set_la_kernel", i32, [p, i32])
+    _sig(L, "hgx_set_ingest_pipeline", i32, [p, i32, i64])
     _sig(L, "hgx_set_incremental", i32, [p, i32])
     _sig(L, "hgx_find_order_begin", i32, [p, p])
     _sig(L, "hgx_find_order_end", i32, [p, p])

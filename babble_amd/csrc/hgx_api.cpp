@@ -658,6 +658,7 @@ int32_t hgx_insert_and_run32(hgx_ctx* c, const hgx_events32* ev, int64_t count, 
         set_err(err, HGX_ERR_INVALID, "hgx_insert_and_run32: bad arguments");
         return HGX_ERR_INVALID;
     }
+    c->eng.pipe_used = 0;
     if (count < 65536 || c->rooted || c->shard_world > 1) {
         int32_t rc = hgx_insert_events32(c, ev, count, n_inserted, err);
         if (rc) return rc;
@@ -666,7 +667,13 @@ int32_t hgx_insert_and_run32(hgx_ctx* c, const hgx_events32* ev, int64_t count, 
     DeviceGuard dg(c);
     const int64_t E0 = c->eng.E;
     hgx::InsertOut out;
-    hipError_t e = c->eng.insert_split_begin32(ev->creator, ev->index, ev->self_parent, ev->other_parent, count, out);
+    // a large first batch: inserted, laid out and its lastAncestors started piece by piece while the
+    // later columns still cross PCIe; otherwise, or after a failed check, as before
+    bool piped = false;
+    hipError_t e = c->grp ? hipSuccess
+                          : c->eng.insert_pipe32(ev->creator, ev->index, ev->self_parent, ev->other_parent, count, out, piped);
+    if (e != hipSuccess) return dev_err(err, e, "hgx_insert_and_run32");
+    if (!piped) e = c->eng.insert_split_begin32(ev->creator, ev->index, ev->self_parent, ev->other_parent, count, out);
     if (e != hipSuccess) return dev_err(err, e, "hgx_insert_and_run32");
     e = c->eng.payload_begin32(ev->timestamp_ns, ev->coin, ev->sig_s, ev->ntx, out.accepted);
     if (e != hipSuccess) return dev_err(err, e, "hgx_insert_and_run32");
@@ -2685,8 +2692,8 @@ int32_t hgx_witness(hgx_ctx* c, int64_t x) {
 // ---- instrumentation / knobs ----------------------------------------------------------
 int32_t hgx_phase_times(hgx_ctx* c, double* out, int32_t cap) {
     if (!c || !out) return 0;
-    const int32_t m = std::min<int32_t>(cap, 22);
-    double v[22] = {c->eng.phase_ms[0], c->eng.phase_ms[1], c->eng.phase_ms[2], c->eng.phase_ms[3],
+    const int32_t m = std::min<int32_t>(cap, 23);
+    double v[23] = {c->eng.phase_ms[0], c->eng.phase_ms[1], c->eng.phase_ms[2], c->eng.phase_ms[3],
                     (double)c->eng.la_sweeps, (double)c->eng.R, (double)c->eng.compact,
                     (double)c->eng.la_rows, c->eng.last_rebuild ? 1.0 : 0.0, (double)c->rh.r_lo,
                     c->eng.la_wave_used ? 1.0 : 0.0, (double)c->eng.la_wave_fallbacks,
@@ -2694,7 +2701,7 @@ int32_t hgx_phase_times(hgx_ctx* c, double* out, int32_t cap) {
                     (double)c->eng.round_p_fallbacks, (double)c->eng.round_p_ovf,
                     (double)c->eng.round_p_fail_round, (double)c->eng.round_p_fail_chain,
                     (double)c->eng.round_g_runs, c->eng.la_small_used ? 1.0 : 0.0,
-                    c->eng.la_verified ? 1.0 : 0.0, (double)c->eng.sort_seg_runs};
+                    c->eng.la_verified ? 1.0 : 0.0, (double)c->eng.sort_seg_runs, (double)c->eng.pipe_used};
     for (int32_t i = 0; i < m; i++) out[i] = v[i];
     return m;
 }
@@ -2769,6 +2776,15 @@ int32_t hgx_device_copy(int32_t device, void* dst, const void* src, int64_t byte
                                : hipSuccess;
     if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
     return e == hipSuccess ? HGX_OK : HGX_ERR_DEVICE;
+}
+
+int32_t hgx_set_ingest_pipeline(hgx_ctx* c, int32_t pieces, int64_t min_events) {
+    if (!c || pieces < 0 || pieces > hgx::kPipeMaxPieces || min_events < 0) return HGX_ERR_INVALID;
+    each_shard(c, [&](hgx_ctx* x) {
+        x->eng.pipe_pieces = pieces;
+        x->eng.pipe_min = min_events;
+    });
+    return HGX_OK;
 }
 
 int32_t hgx_set_la_kernel(hgx_ctx* c, int32_t mode) {

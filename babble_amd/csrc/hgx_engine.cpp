@@ -138,6 +138,14 @@ Engine::~Engine() {
     if (h_flag) (void)hipHostFree(h_flag);
     if (h_segc) (void)hipHostFree(h_segc);
     if (df_host) (void)hipHostFree(df_host);
+    if (pipe_thread.joinable()) pipe_thread.join();
+    if (stream_p) {
+        (void)hipStreamSynchronize(stream_p);
+        (void)hipStreamDestroy(stream_p);
+    }
+    for (hipEvent_t e : ev_pc) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ev_lay) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ev_side) if (e) (void)hipEventDestroy(e);
     if (stream_o) (void)hipStreamSynchronize(stream_o);
     for (auto e : ev_o)
         if (e) (void)hipEventDestroy(e);
@@ -791,6 +799,7 @@ hipError_t Engine::insert_impl(const InsertIn& in, int64_t count, InsertOut& out
                                int commit_mode) {
     out = InsertOut();
     const int64_t E0 = E;
+    pipe_ready = false;
     InsertState st = insert_state();
     if (count > 0) {
         // checks, then the commit of the accepted prefix and the withdrawal of the rest's claims:
@@ -857,7 +866,199 @@ hipError_t Engine::clear() {
     R = 0;
     laid_out = false;
     ids_known = true;
+    pipe_ready = false;
     return hipStreamSynchronize(stream);
+}
+
+// ---- the pipelined ingest --------------------------------------------------
+hipError_t Engine::insert_pipe32(const int32_t* creator, const int32_t* index, const int32_t* sp, const int32_t* op,
+                                 int64_t count, InsertOut& out, bool& taken) {
+    taken = false;
+    pipe_used = 0;
+    if (pipe_pieces <= 0 || count < pipe_min || count < 2 || count > cap || E != 0 || rooted || G != 1 || grp ||
+        time_mask != 0 || la_kernel != 0 || n > 896)
+        return hipSuccess;
+    // the plan's guesses, checked against the histogram: compact coordinates when they are allowed
+    // and the mean chain fits, and the time segments that follow from them
+    const int guess = (!force_coord32 && (n % 2) == 0 && count / C <= 65533) ? 1 : 0;
+    // The segments: a segment's pass is bound by its own DAG depth (c3: 3.3 ms for 1 220 rows per
+    // chain, alone on the device or beside 31 others), and a serial rebuild takes as many as the CUs
+    // hold at once. Here the early pieces' passes run while the later columns are still on the way,
+    // so shorter segments shorten the tail behind the last piece: kPipeSegMult times the serial
+    // choice, still of at least 2 x kLaHeadRows rows per chain
+    const int base = rebuild_segments(count, guess);
+    if (base < 2) return hipSuccess;
+    const int nts = la_segs_override > 0
+                        ? base
+                        : std::max(base, (int)std::min<int64_t>((int64_t)kPipeSegMult * base, count / C / (2 * kLaHeadRows)));
+    const int pieces = std::min(std::min(pipe_pieces, (int)kPipeMaxPieces), nts);
+    int seg_cut[kPipeMaxPieces + 1];
+    int64_t cut[kPipeMaxPieces + 1];
+    for (int k = 0; k <= pieces; k++) {
+        seg_cut[k] = (int)((int64_t)nts * k / pieces);
+        cut[k] = count * seg_cut[k] / nts;   // (k_la_wave's segment bounds)
+    }
+    const size_t c = (size_t)count, Cz = (size_t)C;
+    if (st_creator.n < c) HGX_TRY(st_creator.alloc(c));
+    if (st_index32.n < c) HGX_TRY(st_index32.alloc(c));
+    if (st_sp32.n < c) HGX_TRY(st_sp32.alloc(c));
+    if (st_op32.n < c) HGX_TRY(st_op32.alloc(c));
+    const size_t o_hist = 64, o_lim = o_hist + kPipeMaxPieces * Cz;
+    if (pipe_buf.n < o_lim + kPipeMaxPieces * Cz) HGX_TRY(pipe_buf.alloc(o_lim + kPipeMaxPieces * Cz));
+    if (!stream2) {
+        HGX_TRY(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));
+        HGX_TRY(hipEventCreateWithFlags(&ev_pay, hipEventDisableTiming));
+    }
+    if (!stream_o) {
+        HGX_TRY(hipStreamCreateWithFlags(&stream_o, hipStreamNonBlocking));
+        for (int k = 0; k <= kOrderParts; k++) HGX_TRY(hipEventCreateWithFlags(&ev_o[k], hipEventDisableTiming));
+    }
+    if (!stream_p) {
+        HGX_TRY(hipStreamCreateWithFlags(&stream_p, hipStreamNonBlocking));
+        for (hipEvent_t& e : ev_pc) HGX_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        for (hipEvent_t& e : ev_lay) HGX_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        for (hipEvent_t& e : ev_side) HGX_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    HGX_TRY(payload_wait_S());
+    if (pay_thread.joinable()) pay_thread.join();   // (stream2 is free)
+    if (pipe_thread.joinable()) pipe_thread.join();
+    pipe_err = hipSuccess;
+    pipe_stage = 0;
+    pipe_stop = 0;
+    // one copier: the creator column, then index / sp / op piece by piece, an event behind each
+    // (a host thread: a copy from pageable memory returns only once its source has been consumed)
+    std::vector<int64_t> cuts(cut, cut + pieces + 1);
+    pipe_thread = std::thread([=]() {
+        hipError_t e = hipSetDevice(dev);
+        if (e == hipSuccess) e = hipMemcpyAsync(st_creator.p, creator, c * 4, hipMemcpyHostToDevice, stream2);
+        if (e == hipSuccess) e = hipEventRecord(ev_pc[0], stream2);
+        if (e != hipSuccess) pipe_err = e;
+        pipe_stage.store(1, std::memory_order_release);
+        for (int k = 0; k < pieces; k++) {
+            if (pipe_stop.load(std::memory_order_acquire)) break;
+            const size_t g0 = (size_t)cuts[k], m = (size_t)(cuts[k + 1] - cuts[k]);
+            if (e == hipSuccess) e = hipMemcpyAsync(st_index32.p + g0, index + g0, m * 4, hipMemcpyHostToDevice, stream2);
+            if (e == hipSuccess) e = hipMemcpyAsync(st_sp32.p + g0, sp + g0, m * 4, hipMemcpyHostToDevice, stream2);
+            if (e == hipSuccess) e = hipMemcpyAsync(st_op32.p + g0, op + g0, m * 4, hipMemcpyHostToDevice, stream2);
+            if (e == hipSuccess) e = hipEventRecord(ev_pc[k + 1], stream2);
+            if (e != hipSuccess) pipe_err = e;
+            pipe_stage.store(k + 2, std::memory_order_release);
+        }
+        const hipError_t es = hipStreamSynchronize(stream2);   // the caller's columns are read completely
+        if (e == hipSuccess && es != hipSuccess) pipe_err = es;
+    });
+    // every way out joins the copier; `fail` leaves the context empty for the serial path
+    auto stop = [&](hipError_t e) {
+        pipe_stop.store(1, std::memory_order_release);
+        if (pipe_thread.joinable()) pipe_thread.join();
+        return e != hipSuccess ? e : pipe_err;
+    };
+    auto wait_stage = [&](int want) {
+        // the event must have been recorded before a stream is made to wait for it
+        while (pipe_stage.load(std::memory_order_acquire) < want) std::this_thread::yield();
+        return pipe_err;
+    };
+#define PIPE_TRY(x)                                  \
+    do {                                             \
+        const hipError_t e_ = (x);                   \
+        if (e_ != hipSuccess) return stop(e_);       \
+    } while (0)
+    int32_t* gate = pipe_buf.p;
+    PIPE_TRY(hipMemsetAsync(pipe_buf.p, 0, (o_hist + (size_t)pieces * Cz) * 4, stream));
+    PIPE_TRY(wait_stage(1));
+    PIPE_TRY(hipStreamWaitEvent(stream, ev_pc[0], 0));
+    launch_pipe_hist(stream, pieces, cut, C, st_creator.p, pipe_buf.p + o_hist);
+    PIPE_TRY(hipGetLastError());
+    pipe_hist.resize((size_t)pieces * Cz);
+    PIPE_TRY(hipMemcpyAsync(pipe_hist.data(), pipe_buf.p + o_hist, pipe_hist.size() * 4, hipMemcpyDeviceToHost, stream));
+    PIPE_TRY(hipStreamSynchronize(stream));
+    // the plan: every chain's rows at the end of each piece, the totals, and what divide_rounds
+    // will derive from them (first Index 0 on every chain: k_pipe_check holds the batch to it)
+    pipe_lim.assign((size_t)pieces * Cz, 0);
+    std::vector<int32_t> len(Cz, 0);
+    int64_t known = 0;
+    int mlen = 0;
+    for (int k = 0; k < pieces; k++)
+        for (size_t ch = 0; ch < Cz; ch++) {
+            len[ch] += pipe_hist[(size_t)k * Cz + ch];
+            pipe_lim[(size_t)k * Cz + ch] = len[ch];
+        }
+    for (size_t ch = 0; ch < Cz; ch++) {
+        known += len[ch];
+        mlen = std::max(mlen, len[ch]);
+    }
+    const int plan_compact = (!force_coord32 && (n % 2) == 0 && mlen - 1 <= 65533) ? 1 : 0;
+    if (known != count || plan_compact != guess || !la_wave_ok(n, mlen, n)) {
+        PIPE_TRY(stop(hipSuccess));
+        return hipSuccess;   // (an unknown creator, or very uneven chains: the serial path)
+    }
+    compact = plan_compact;
+    layout_slots(count, len, pipe_off);
+    std::memcpy(h_cpar, len.data(), Cz * 4);
+    std::memset(h_cpar + C, 0, 2 * Cz * 4);   // c_base, c_old
+    PIPE_TRY(hipMemcpyAsync(c_off.p, pipe_off.data(), (Cz + 1) * 4, hipMemcpyHostToDevice, stream));
+    PIPE_TRY(hipMemcpyAsync(cpar_blk.p, h_cpar, 3 * Cz * 4, hipMemcpyHostToDevice, stream));
+    PIPE_TRY(hipMemcpyAsync(pipe_buf.p + o_lim, pipe_lim.data(), pipe_lim.size() * 4, hipMemcpyHostToDevice, stream));
+    const DevArrays a = arrays();
+    const InsertState st = insert_state();
+    for (int k = 0; k < pieces; k++) {
+        const int64_t g0 = cut[k], g1 = cut[k + 1];
+        PIPE_TRY(wait_stage(k + 2));
+        PIPE_TRY(hipStreamWaitEvent(stream, ev_pc[k + 1], 0));
+        InsertIn in{};
+        in.creator = st_creator.p + g0; in.index32 = st_index32.p + g0; in.sp32 = st_sp32.p + g0; in.op32 = st_op32.p + g0;
+        launch_pipe_insert(stream, g1 - g0, g0, cap, C, n, in, st, gate);
+        launch_layout(stream, g0, g1, a, C, n, kLaSeg, gate);
+        PIPE_TRY(hipGetLastError());
+        PIPE_TRY(hipEventRecord(ev_lay[k], stream));
+        // the piece's segments, beside the next piece's copy, insert and layout
+        hipStream_t side = (k & 1) ? stream_p : stream_o;
+        PIPE_TRY(hipStreamWaitEvent(side, ev_lay[k], 0));
+        LaSubset sub;
+        sub.first = seg_cut[k]; sub.count = seg_cut[k + 1] - seg_cut[k];
+        sub.c_lim = pipe_buf.p + o_lim + (size_t)k * Cz; sub.gate = gate;
+        PIPE_TRY(launch_la_wave(side, a, 1, n, nullptr, count, nts, 0, counters.p + 6, nullptr, n, false, sub));
+    }
+    PIPE_TRY(hipEventRecord(ev_side[0], stream_o));
+    PIPE_TRY(hipStreamWaitEvent(stream, ev_side[0], 0));
+    if (pieces > 1) {
+        PIPE_TRY(hipEventRecord(ev_side[1], stream_p));
+        PIPE_TRY(hipStreamWaitEvent(stream, ev_side[1], 0));
+    }
+    // one read-back, as insert_impl: the first-failure word (re-armed) and the state block
+    PIPE_TRY(copy_to_pinned(h_small, ins_fail.p, 8, 0xFF));
+    PIPE_TRY(copy_to_pinned(h_ins, ins_blk.p, ins_blk.n * sizeof(int32_t)));
+    PIPE_TRY(stage_issue());
+    PIPE_TRY(hipStreamSynchronize(stream));
+    PIPE_TRY(stop(hipSuccess));
+#undef PIPE_TRY
+    unsigned long long fail = 0;
+    std::memcpy(&fail, h_small, 8);
+    if (fail != ~0ull) {
+        // a check failed in some piece: empty the context again (the claims of every piece issued
+        // so far included) and let the serial path produce the error and the accepted prefix
+        E = count;
+        return clear();
+    }
+    E = count;
+    split32 = true;
+    out = InsertOut();
+    out.accepted = count;
+    out.last_gid.resize(C);
+    out.last_index.resize(C);
+    out.chain_base.resize(C);
+    out.graph_loaded.resize(G);
+    std::memcpy(out.last_gid.data(), h_ins, Cz * 4);
+    std::memcpy(out.last_index.data(), h_ins + C, Cz * 4);
+    std::memcpy(out.chain_base.data(), h_ins + 2 * C, Cz * 4);
+    std::memcpy(out.graph_loaded.data(), h_ins + ins_gl_off, (size_t)G * 8);
+    pipe_ready = true;
+    pipe_En = count;
+    pipe_nts = nts;
+    pipe_compact = plan_compact;
+    pipe_used = pieces;
+    taken = true;
+    return hipSuccess;
 }
 
 // ---- hgx_prune_to_frame (hgx_compact.hip) ---------------------------------
@@ -1223,6 +1424,29 @@ hipError_t Engine::capture_steps(StepGraph& sgr, const RoundArgs& args, int kern
     return hipSuccess;
 }
 
+// The slots of a rebuilt layout and the time segments of its lastAncestors pass: one place for
+// divide_rounds and the pipelined ingest, which lays the chains out before divide_rounds runs
+void Engine::layout_slots(int64_t En, const std::vector<int32_t>& chain_len, std::vector<int32_t>& off) const {
+    int act = 0;
+    for (int c = 0; c < C; c++) act += chain_len[c] > 0 ? 1 : 0;
+    const int64_t share = (Ppos - En) / (2 * (int64_t)act + (C - act));
+    off.assign(C + 1, 0);
+    // slots of multiples of 32 positions (a share >= 128 > 31: Ppos >= capacity + 256 C): every
+    // chain starts 64-byte aligned in the firstDescendants columns (the round kernels' staging)
+    for (int c = 0; c < C; c++)
+        off[c + 1] = off[c] + ((chain_len[c] + (int32_t)((chain_len[c] > 0 ? 2 : 1) * share)) & ~31);
+}
+
+int Engine::rebuild_segments(int64_t En, int coord_compact) const {
+    if (G != 1 || En < (int64_t)kLaSegMinRows * C) return 1;
+    // as many segments as the CUs hold, of at least 2 x kLaHeadRows rows per chain: c2 (64 chains
+    // of 16 384 rows, 4 column blocks) took 2.04 ms at 16 segments, 0.69 at 128, and at 192 its
+    // exactness check failed (the verify sweep ran); c3 keeps its LDS-bound 16 (profiles/r05/b28_*, b29_*)
+    // (the round-4 cap of kLaMaxSegs alone: c2 2.04 ms)
+    const int cap_segs = (int)std::max<int64_t>(kLaMaxSegs, En / C / (2 * kLaHeadRows));
+    return la_segs_override > 0 ? la_segs_override : la_wave_segments(n, coord_compact, num_cus, cap_segs);
+}
+
 // ---- DivideRounds ---------------------------------------------------------------
 // Chains are laid out with slack (positions [c_off[c], c_off[c] + slot)), so that a call
 // after more InsertEvents only appends rows: the events of earlier calls keep their
@@ -1257,14 +1481,7 @@ hipError_t Engine::divide_rounds(int64_t En, const std::vector<int32_t>& chain_l
         // one that has not created an event yet). With even shares c5's 341 silent peers held a
         // third of the slack and the live chains outgrew theirs two thirds through the run (an
         // 18.8 ms rebuild call)
-        int act = 0;
-        for (int c = 0; c < C; c++) act += chain_len[c] > 0 ? 1 : 0;
-        const int64_t share = (Ppos - En) / (2 * (int64_t)act + (C - act));
-        h_off.assign(C + 1, 0);
-        // slots of multiples of 32 positions (a share >= 128 > 31: Ppos >= capacity + 256 C): every
-        // chain starts 64-byte aligned in the firstDescendants columns (the round kernels' staging)
-        for (int c = 0; c < C; c++)
-            h_off[c + 1] = h_off[c] + ((chain_len[c] + (int32_t)((chain_len[c] > 0 ? 2 : 1) * share)) & ~31);
+        layout_slots(En, chain_len, h_off);
         HGX_TRY(hipMemcpyAsync(c_off.p, h_off.data(), (C + 1) * 4, hipMemcpyHostToDevice, stream));
         h_len_div.assign(C, 0);
         last_rebuild = true;
@@ -1302,9 +1519,6 @@ hipError_t Engine::divide_rounds(int64_t En, const std::vector<int32_t>& chain_l
     DevArrays a = arrays();
     HGX_TRY(hipEventRecord(ph0, stream));
     const int seg = kLaSeg;
-    kbeg(K_LAYOUT);
-    launch_layout(stream, E0, En, a, C, n, seg);
-    kend(K_LAYOUT, (double)(En - E0) * 64);
     // lastAncestors: fixed point from all -1 (new rows), dirty-tracked sweeps (k_la_sweep)
     const size_t nunits = (size_t)((max_len + seg - 1) / seg) * C;
     int64_t u0 = 0;
@@ -1326,15 +1540,14 @@ hipError_t Engine::divide_rounds(int64_t En, const std::vector<int32_t>& chain_l
     la_wave_used = la_kernel == 0 && la_wave_ok(n, max_len, la_na) && (n <= 896 || la_map);
     // a rebuild of one large graph runs the wavefront on time segments in parallel (their
     // rows are lower bounds), then a verify sweep and the dirty sweeps complete them
-    la_wave_segs = 1;
-    if (la_wave_used && rebuild && G == 1 && En >= (int64_t)kLaSegMinRows * C) {
-        // as many segments as the CUs hold, of at least 2 x kLaHeadRows rows per chain: c2 (64 chains
-        // of 16 384 rows, 4 column blocks) took 2.04 ms at 16 segments, 0.69 at 128, and at 192 its
-        // exactness check failed (the verify sweep ran); c3 keeps its LDS-bound 16 (profiles/r05/b28_*, b29_*)
-        // (the round-4 cap of kLaMaxSegs alone: c2 2.04 ms)
-        const int cap = (int)std::max<int64_t>(kLaMaxSegs, En / C / (2 * kLaHeadRows));
-        la_wave_segs = la_segs_override > 0 ? la_segs_override : la_wave_segments(n, compact, num_cus, cap);
-    }
+    // the pipelined ingest laid these events out and ran the main pass of its segments already
+    const bool piped = pipe_ready && rebuild && la_wave_used && !la_map && pipe_nts > 1 && En == pipe_En &&
+                       compact == pipe_compact && h_off == pipe_off;
+    pipe_ready = false;
+    la_wave_segs = piped ? pipe_nts : (la_wave_used && rebuild) ? rebuild_segments(En, compact) : 1;
+    kbeg(K_LAYOUT);
+    if (!piped) launch_layout(stream, E0, En, a, C, n, seg);
+    kend(K_LAYOUT, (double)(En - E0) * 64);
     if (rebuild) {   // (the wavefront writes every row it builds before anything reads it)
         if (!la_wave_used) HGX_TRY(hipMemsetAsync(LA.p, compact ? 0x00 : 0xFF, (size_t)h_off[C] * n * csz, stream));
     } else {
@@ -1405,7 +1618,7 @@ hipError_t Engine::divide_rounds(int64_t En, const std::vector<int32_t>& chain_l
         const size_t small_lds = (la_wave_segs == 1 && !la_map && la_small_override != 0) ? la_small_bytes(n, compact, gpos) : 0;
         la_small_used = small_lds > 0;
         if (la_small_used) HGX_TRY(launch_la_small(stream, a, G, n, cold, small_lds, counters.p + 6));
-        else
+        else if (!piped)
             HGX_TRY(launch_la_wave(stream, a, G, n, cold, En, la_wave_segs, 0, counters.p + 6, la_map, la_na,
                                    !rebuild && (En - E0) <= 8 * (int64_t)C));
         if (la_wave_segs > 1)

@@ -249,6 +249,18 @@ class Engine {
                            std::vector<uint8_t>& coin, std::vector<int32_t>& ntx, std::vector<uint8_t>& txnil);
     hipError_t divide_rounds(int64_t E, const std::vector<int32_t>& chain_len,
                              const std::vector<int32_t>& chain_base, RoundsHost& out);
+    // The pipelined ingest of a large first batch (compact columns in host memory):
+    // the creator column is copied first and gives the layout plan; the other structure columns
+    // follow in pieces cut at time-segment boundaries, and each piece is inserted, laid out and its
+    // segments' lastAncestors main pass launched while the later pieces still cross PCIe. taken =
+    // false: nothing was inserted (the path does not apply, or a check failed and the context was
+    // cleared) and the caller runs insert_split_begin32 on the same columns.
+    hipError_t insert_pipe32(const int32_t* creator, const int32_t* index, const int32_t* sp, const int32_t* op,
+                             int64_t count, InsertOut& out, bool& taken);
+    static constexpr int kPipeSegMult = 2;   // time segments of a pipelined ingest over a serial rebuild's
+    int pipe_pieces = 4;                // hgx_set_ingest_pipeline: 0 = always the serial path
+    int64_t pipe_min = 4000000;         // ... batches of at least this many events
+    int pipe_used = 0;                  // pieces of the last insert_and_run32 (0: serial)
     // fame of the witnesses of rounds >= r0 (the first undecided round); rows below stay 0
     hipError_t decide_fame(int32_t r0, std::vector<int8_t>& fame_out);
     // round received etc. for the events not yet received; r0 / max_unrecv from recv_round_lo
@@ -338,6 +350,20 @@ class Engine {
     hipError_t insert_impl(const InsertIn& in, int64_t count, InsertOut& out, const unsigned long long* fail_sig,
                            int commit_mode = kCommitAll);
     hipStream_t stream2 = nullptr;   // payload copies of insert_split (created on first use)
+    // the pipelined ingest: stream_p and stream_o take the pieces' k_la_wave launches in turn
+    void layout_slots(int64_t En, const std::vector<int32_t>& chain_len, std::vector<int32_t>& off) const;
+    int rebuild_segments(int64_t En, int coord_compact) const;
+    hipStream_t stream_p = nullptr;
+    hipEvent_t ev_pc[kPipeMaxPieces + 1] = {}, ev_lay[kPipeMaxPieces] = {}, ev_side[2] = {};
+    std::atomic<int> pipe_stage{0};   // 1: the creator column issued and ev_pc[0] recorded, k + 2: piece k
+    std::atomic<int> pipe_stop{0};
+    std::thread pipe_thread;
+    hipError_t pipe_err = hipSuccess;
+    DBuf<int32_t> pipe_buf;           // [0] the gate word, [64 ..) the histogram, then the pieces' chain lengths
+    std::vector<int32_t> pipe_hist, pipe_lim, pipe_off;
+    bool pipe_ready = false;          // layout and main pass done for pipe_En / pipe_nts / pipe_off / pipe_compact
+    int64_t pipe_En = 0;
+    int pipe_nts = 0, pipe_compact = 0;
     bool pay32 = false;              // the payload in flight is hgx_events32's (coin byte, ntx -1 = nil)
     bool split32 = false;            // the structure columns staged by insert_split_begin32
     hipEvent_t ev_pay = nullptr;

@@ -331,6 +331,85 @@ void launch_insert_unclaim(hipStream_t s, int64_t m, const unsigned long long* f
         hipLaunchKernelGGL(k_insert_unclaim, dim3(nblocks(m)), dim3(256), 0, s, m, fail, fail_sig, E0, cap, C, in, st);
 }
 
+// ---- the pipelined ingest (Engine::insert_pipe32) ---------------------------
+// A large first batch is inserted in pieces (gid ranges) while its later columns still cross PCIe:
+// per piece claim -> check -> commit(structure) with E0 = the piece's first gid, which is the batch
+// rule applied to consecutive batches. `gate` is the path's cumulative failure word: the commit of
+// a piece whose check failed commits nothing and sets it, and every later launch of the path
+// (these kernels, the layout, k_la_wave) then does nothing. The host redoes the whole batch on the
+// serial path, which produces the error and the accepted prefix.
+
+// events per (piece, chain) from the creator column alone: piece k = batch positions [cut[k], cut[k + 1])
+struct PipeCuts {
+    int64_t cut[kPipeMaxPieces + 1];
+};
+__global__ void __launch_bounds__(256) k_pipe_hist(PipeCuts pc, int C, const int32_t* __restrict__ creator,
+                                                   int32_t* __restrict__ hist) {
+    extern __shared__ int32_t s_h[];   // [C]
+    const int piece = blockIdx.y;
+    for (int c = threadIdx.x; c < C; c += blockDim.x) s_h[c] = 0;
+    __syncthreads();
+    const int64_t k1 = pc.cut[piece + 1];
+    for (int64_t k = pc.cut[piece] + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < k1;
+         k += (int64_t)gridDim.x * blockDim.x) {
+        const int cr = creator[k];
+        if (cr >= 0 && cr < C) atomicAdd(&s_h[cr], 1);   // (an unknown creator fails its piece's check)
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += blockDim.x)
+        if (s_h[c]) atomicAdd(&hist[(size_t)piece * C + c], s_h[c]);
+}
+
+void launch_pipe_hist(hipStream_t s, int pieces, const int64_t* cut, int C, const int32_t* creator, int32_t* hist) {
+    PipeCuts pc{};
+    int64_t most = 0;
+    for (int k = 0; k <= pieces; k++) pc.cut[k] = cut[k];
+    for (int k = 0; k < pieces; k++) most = cut[k + 1] - cut[k] > most ? cut[k + 1] - cut[k] : most;
+    // at least 4 096 events per block (its LDS histogram is flushed with one atomic per chain), at most 256 blocks per piece
+    int64_t blocks = (most + 4095) / 4096;
+    blocks = blocks < 1 ? 1 : blocks > 256 ? 256 : blocks;
+    const unsigned bx = (unsigned)blocks;
+    hipLaunchKernelGGL(k_pipe_hist, dim3(bx, (unsigned)pieces), dim3(256), (size_t)C * 4, s, pc, C, creator, hist);
+}
+
+__global__ void __launch_bounds__(256) k_pipe_claim(int64_t m, int64_t E0, int64_t cap, int C, InsertIn in,
+                                                    InsertState st, const int32_t* __restrict__ gate) {
+    if (*gate) return;
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < m) ins_claim(k, E0, cap, C, in, st);
+}
+
+// the layout plan was made for chains whose first Index is 0 (the creator column alone cannot tell):
+// any other first Index sends the batch to the serial path like a failed check
+__global__ void __launch_bounds__(256) k_pipe_check(int64_t m, int64_t E0, int64_t cap, int C, int n, InsertIn in,
+                                                    InsertState st, const int32_t* __restrict__ gate) {
+    if (*gate) return;
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= m) return;
+    ins_check(k, E0, cap, C, n, in, st);
+    if (in.sp_at(k) == -1 && in.idx_at(k) != 0) atomicMin(st.fail, ((unsigned long long)k << 8) | 0xFFull);
+}
+
+__global__ void __launch_bounds__(256) k_pipe_commit(int64_t m, int64_t E0, int n, InsertIn in, InsertState st,
+                                                     int32_t* __restrict__ gate) {
+    // (the word is final: the piece's check finished before this launch, and gated launches leave it alone)
+    if (*st.fail != ~0ull) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) *gate = 1;
+        return;
+    }
+    ins_commit(m, nullptr, nullptr, E0, n, in, st, kCommitStructure, (int64_t)blockIdx.x * blockDim.x,
+               (int64_t)gridDim.x * blockDim.x);
+}
+
+void launch_pipe_insert(hipStream_t s, int64_t m, int64_t E0, int64_t cap, int C, int n, const InsertIn& in,
+                        const InsertState& st, int32_t* gate) {
+    if (m <= 0) return;
+    hipLaunchKernelGGL(k_pipe_claim, dim3(nblocks(m)), dim3(256), 0, s, m, E0, cap, C, in, st, gate);
+    hipLaunchKernelGGL(k_pipe_check, dim3(nblocks(m)), dim3(256), 0, s, m, E0, cap, C, n, in, st, gate);
+    const unsigned grid = nblocks(m) < 4096u ? nblocks(m) : 4096u;
+    hipLaunchKernelGGL(k_pipe_commit, dim3(grid), dim3(256), 0, s, m, E0, n, in, st, gate);
+}
+
 // hgx_events_packed's structure columns decoded into the hgx_events32 form (include/hgx.h): a parent
 // d back from the event's gid E0 + k, 0 = "", kEscape = its exception entry (k_unpack_exc, launched
 // after this on the same stream; without one it reads as HGX_UNKNOWN_PARENT). Two events per thread:

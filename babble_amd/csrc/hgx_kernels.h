@@ -155,7 +155,9 @@ void launch_copy_many(hipStream_t s, const CopyRange* r, int count);
 int fd_tile_rows(int n, int compact);
 // gid order -> chain-major positions; p_opu = lastAncestors unit of the op row (SEG rows),
 // p_opk = packed op chain and row (gids [E0, E))
-void launch_layout(hipStream_t s, int64_t E0, int64_t E, const DevArrays& a, int C, int n, int seg);
+// gate (the pipelined ingest): a device word that makes the launch do nothing when non-zero
+void launch_layout(hipStream_t s, int64_t E0, int64_t E, const DevArrays& a, int C, int n, int seg,
+                   const int32_t* gate = nullptr);
 // lastAncestors of the new rows (from c_old[c], all rows when c_old is null) in ONE pass:
 // per (graph, 16-byte column block) a workgroup whose lanes own the chains and wait for
 // their op rows in an LDS ring. Needs n <= 896 and chains < 2^kOpkBits
@@ -180,9 +182,17 @@ int la_wave_segments(int n, int compact, int num_cus, int max_segs);   // time s
 // |= 1 unless every row is provably exact (then no verify sweep is needed); tbl: (nts + 1) x n ints
 hipError_t launch_la_seg_check(hipStream_t s, const DevArrays& a, int n, int64_t E, int nts, int head, int32_t* tbl,
                                int32_t* flag);
+// sub (the pipelined ingest): the main pass (head == 0) of the time segments [first, first +
+// count) alone, once the events below E (first + count) / nts are laid out: c_lim[c] = chain c's rows laid
+// out by then (the segment bounds are searched below it), gate = a device word that cancels the launch
+struct LaSubset {
+    int first = 0, count = 0;   // count == 0: every segment
+    const int32_t* c_lim = nullptr;
+    const int32_t* gate = nullptr;
+};
 hipError_t launch_la_wave(hipStream_t s, const DevArrays& a, int G, int n, const int32_t* c_old, int64_t E, int nts,
                           int head, int32_t* err, const int32_t* lmap = nullptr, int na = 0,
-                          bool narrow = false);
+                          bool narrow = false, const LaSubset& sub = LaSubset());
 // one Gauss-Seidel sweep over the dirty units (all when `first`) from unit u0: a unit is dirty
 // when its carry unit or an op unit has chg == stamp - 1, and gets chg = stamp when its values
 // change (usum = per-unit sums); out[0] += rows recomputed, out[1] += units changed; out_next
@@ -330,6 +340,13 @@ constexpr int kCommitAll = 0, kCommitStructure = 1, kCommitPayload = 2;
 // m_ok = the accepted prefix of m from the first-failure words (all m when fail is null)
 void launch_insert_commit(hipStream_t s, int64_t m, const unsigned long long* fail, const unsigned long long* fail_sig,
                           int64_t E0, int n, const InsertIn& in, const InsertState& st, int mode);
+// the pipelined ingest (hgx_insert.hip): events per (piece, chain) of the creator column, hist[pieces][C]
+// zeroed by the caller, piece k = batch positions [cut[k], cut[k + 1]); and one piece's claim, check
+// and structure commit, cancelled by (and on a failed check setting) the word *gate
+constexpr int kPipeMaxPieces = 8;
+void launch_pipe_hist(hipStream_t s, int pieces, const int64_t* cut, int C, const int32_t* creator, int32_t* hist);
+void launch_pipe_insert(hipStream_t s, int64_t m, int64_t E0, int64_t cap, int C, int n, const InsertIn& in,
+                        const InsertState& st, int32_t* gate);
 void launch_ts_to_pos(hipStream_t s, int64_t E0, int64_t m, const int32_t* g_pos, const int64_t* g_ts, int64_t* p_ts);
 void launch_insert_unclaim(hipStream_t s, int64_t m, const unsigned long long* fail, const unsigned long long* fail_sig,
                            int64_t E0, int64_t cap, int C, const InsertIn& in, const InsertState& st);

@@ -37,7 +37,8 @@ constexpr int kLayoutH = 1024;   // chain-id range a block can group (else direc
 // so each gather was a line of its own (c4: 204 bytes fetched per laid-out event)
 __global__ void __launch_bounds__(256) k_ck_pack(int64_t E0, int64_t E, const int32_t* __restrict__ g_creator,
                                                  const int32_t* __restrict__ g_index, const int32_t* __restrict__ c_base,
-                                                 int64_t* __restrict__ g_ck) {
+                                                 int64_t* __restrict__ g_ck, const int32_t* __restrict__ gate) {
+    if (gate && *gate) return;   // (the pipelined ingest: an earlier piece failed its checks)
     const int64_t gid = E0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= E) return;
     const int c = g_creator[gid];
@@ -87,7 +88,8 @@ __global__ void __launch_bounds__(256) k_layout_direct(int64_t E0, int64_t E, co
                                                        int32_t* __restrict__ p_op, int32_t* __restrict__ p_opu,
                                                        int32_t* __restrict__ p_opk, int64_t* __restrict__ p_ts,
                                                        int32_t* __restrict__ p_rr, int64_t* __restrict__ p_cts, int C,
-                                                       int n, int seg) {
+                                                       int n, int seg, const int32_t* __restrict__ gate) {
+    if (gate && *gate) return;
     const int64_t gid = E0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= E) return;
     const int c = g_creator[gid];
@@ -114,8 +116,10 @@ __global__ void __launch_bounds__(256) k_layout_staged(int64_t E0, int64_t E, co
                                                        int32_t* __restrict__ p_chain, int32_t* __restrict__ p_op,
                                                        int32_t* __restrict__ p_opu, int32_t* __restrict__ p_opk,
                                                        int64_t* __restrict__ p_ts, int32_t* __restrict__ p_rr,
-                                                       int64_t* __restrict__ p_cts, int C, int n, int seg) {
+                                                       int64_t* __restrict__ p_cts, int C, int n, int seg,
+                                                       const int32_t* __restrict__ gate) {
     constexpr int B = kLayoutB2, PT = B / 256;   // events per thread
+    if (gate && *gate) return;   // (block-uniform)
     __shared__ int32_t s_cnt[kLayoutH], s_min[kLayoutH];
     __shared__ int32_t s_slot[B];   // slot -> gid offset in the block
     __shared__ int32_t s_cr[B], s_ix[B];
@@ -2279,19 +2283,19 @@ void launch_copy_many(hipStream_t s, const CopyRange* r, int count) {
     hipLaunchKernelGGL(k_copy_many, dim3(bx, std::min(count, kCopyMax)), dim3(256), 0, s, f);
 }
 
-void launch_layout(hipStream_t s, int64_t E0, int64_t E, const DevArrays& a, int C, int n, int seg) {
+void launch_layout(hipStream_t s, int64_t E0, int64_t E, const DevArrays& a, int C, int n, int seg, const int32_t* gate) {
     if (E <= E0) return;
     hipLaunchKernelGGL(k_ck_pack, dim3(nblk(E - E0, 256)), dim3(256), 0, s, E0, E, a.g_creator, a.g_index, a.c_base,
-                       a.g_ck);
+                       a.g_ck, gate);
     if (E - E0 <= 8 * kLayoutB) {
         hipLaunchKernelGGL(k_layout_direct, dim3(nblk(E - E0, 256)), dim3(256), 0, s, E0, E, a.g_creator, a.g_index,
                            a.g_ck, a.g_op, a.g_ts, a.g_rr, a.g_cts, a.c_off, a.c_base, a.g_pos, a.p_gid, a.p_chain, a.p_op,
-                           a.p_opu, a.p_opk, a.p_ts, a.p_rr, a.p_cts, C, n, seg);
+                           a.p_opu, a.p_opk, a.p_ts, a.p_rr, a.p_cts, C, n, seg, gate);
         return;
     }
     hipLaunchKernelGGL(k_layout_staged, dim3(nblk(E - E0, kLayoutB2)), dim3(256), 0, s, E0, E, a.g_creator, a.g_index,
                        a.g_ck, a.g_op, a.g_ts, a.g_rr, a.g_cts, a.c_off, a.c_base, a.g_pos, a.p_gid, a.p_chain, a.p_op,
-                       a.p_opu, a.p_opk, a.p_ts, a.p_rr, a.p_cts, C, n, seg);
+                       a.p_opu, a.p_opk, a.p_ts, a.p_rr, a.p_cts, C, n, seg, gate);
 }
 
 void launch_la_sweep(hipStream_t s, const DevArrays& a, int C, int n, int max_len, int seg, int first, int32_t* chg,

@@ -166,8 +166,11 @@ __global__ void __launch_bounds__(1024) k_la_wave(uint32_t* __restrict__ LA, con
                                                   const int32_t* __restrict__ c_old,
                                                   const int32_t* __restrict__ p_gid, int64_t E, int nts, int head,
                                                   int n, int lgnp, int nwd, int nblk, int32_t* __restrict__ err,
-                                                  const int32_t* __restrict__ lmap, int na) {
+                                                  const int32_t* __restrict__ lmap, int na, int ts0,
+                                                  const int32_t* __restrict__ c_lim,
+                                                  const int32_t* __restrict__ gate) {
     typedef LaW<CT> W;
+    if (gate && *gate) return;   // (the pipelined ingest: a piece failed its checks, nothing is laid out)
     extern __shared__ uint32_t smem[];
     // slot-major arrays with a power-of-two chain stride NP = 2^lgnp >= n (index = shifts)
     const int NP = 1 << lgnp;
@@ -180,7 +183,8 @@ __global__ void __launch_bounds__(1024) k_la_wave(uint32_t* __restrict__ LA, con
     int32_t* s_off = s_old + n;
     int32_t* s_len = s_off + n;
     int32_t* s_abort = s_len + n;
-    const int b = blockIdx.x % nblk, ts = (blockIdx.x / nblk) % nts, g = blockIdx.x / nblk / nts;
+    // (a subset launch, MODE 2 of one graph: the grid holds the segments from ts0 on)
+    const int b = blockIdx.x % nblk, ts = ts0 + (blockIdx.x / nblk) % nts, g = blockIdx.x / nblk / nts;
     const int c0 = g * n;
     const int wb = b * DW;   // first word of the block
     const int tid = threadIdx.x;
@@ -190,8 +194,11 @@ __global__ void __launch_bounds__(1024) k_la_wave(uint32_t* __restrict__ LA, con
         int o = 0, e = len;
         if constexpr (MODE == 1) o = c_old[c0 + t];
         if constexpr (MODE >= 2) {
-            o = ts == 0 ? 0 : chain_lower_bound(p_gid, off, len, E * ts / nts);
-            e = ts == nts - 1 ? len : chain_lower_bound(p_gid, off, len, E * (ts + 1) / nts);
+            // c_lim: the rows laid out so far (a subset launch's segments end at or below them; the
+            // positions above may hold an earlier trace's gids)
+            const int lim = c_lim ? c_lim[c0 + t] : len;
+            o = ts == 0 ? 0 : chain_lower_bound(p_gid, off, lim, E * ts / nts);
+            e = ts == nts - 1 ? lim : chain_lower_bound(p_gid, off, lim, E * (ts + 1) / nts);
             if constexpr (MODE == 3) e = ts == 0 ? o : min(e, o + head);
         }
         lqv[t] = o;
@@ -357,7 +364,7 @@ __global__ void __launch_bounds__(1024) k_la_wave(uint32_t* __restrict__ LA, con
 namespace {
 template <typename CT, int DW, int R, int Q, int NLW, int J, int CH, int MODE>
 hipError_t la_wave_launch1(hipStream_t s, const DevArrays& a, int G, int n, const int32_t* c_old, int64_t E, int nts,
-                           int head, int32_t* err, const int32_t* lmap, int na) {
+                           int head, int32_t* err, const int32_t* lmap, int na, const LaSubset& sub = LaSubset()) {
     const int nwd = a.compact ? n / 2 : n;
     const int nblk = nwd / DW;
     int lgnp = 0;
@@ -371,8 +378,10 @@ hipError_t la_wave_launch1(hipStream_t s, const DevArrays& a, int G, int n, cons
     }
     const int threads = (((lmap ? na : n) + 63) & ~63) + 64 * NLW;
     if (threads > 1024 || (lmap && G != 1)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(kern, dim3(G * nts * nblk), dim3(threads), words * 4, s, (uint32_t*)a.LA, a.p_opk, a.c_off,
-                       a.c_len, a.c_base, c_old, a.p_gid, E, nts, head, n, lgnp, nwd, nblk, err, lmap, na);
+    const int nseg = sub.count > 0 ? sub.count : nts;   // (a subset: one graph, MODE 2)
+    hipLaunchKernelGGL(kern, dim3(G * nseg * nblk), dim3(threads), words * 4, s, (uint32_t*)a.LA, a.p_opk, a.c_off,
+                       a.c_len, a.c_base, c_old, a.p_gid, E, nts, head, n, lgnp, nwd, nblk, err, lmap, na, sub.first,
+                       sub.c_lim, sub.gate);
     return hipGetLastError();
 }
 template <typename CT, int DW, int R, int Q, int NLW, int J, int CH>
@@ -398,14 +407,15 @@ inline SegCfg seg_cfg(int n, int nwd) {
 // LDS: NP * (R * DW + R + Q) + 5 n words <= 160 KB (NP = n rounded up to a power of two); DW divides the row's words
 template <typename CT>
 hipError_t la_wave_dispatch(hipStream_t s, const DevArrays& a, int G, int n, const int32_t* c_old, int64_t E, int nts,
-                            int head, int32_t* err, const int32_t* lmap, int na, bool narrow) {
+                            int head, int32_t* err, const int32_t* lmap, int na, bool narrow, const LaSubset& sub) {
     const int nwd = a.compact ? n / 2 : n;
     if (nts > 1) {   // time segments: wider blocks, smaller rings (seg_cfg)
         const SegCfg g = seg_cfg(n, nwd);
 #define SEG(DW_, R_, Q_, NLW_, J_, CH_)                                                                                \
     return head > 0 ? la_wave_launch1<CT, DW_, R_, Q_, NLW_, J_, CH_, 3>(s, a, G, n, nullptr, E, nts, head, err, lmap, \
                                                                           na)                                          \
-                    : la_wave_launch1<CT, DW_, R_, Q_, NLW_, J_, CH_, 2>(s, a, G, n, nullptr, E, nts, 0, err, lmap, na)
+                    : la_wave_launch1<CT, DW_, R_, Q_, NLW_, J_, CH_, 2>(s, a, G, n, nullptr, E, nts, 0, err, lmap, na, \
+                                                                          sub)
         if (n <= 256) {
             if (g.dw == 16) SEG(16, 8, 16, 1, 4, 8);
             if (g.dw == 8) SEG(8, 8, 32, 1, 4, 8);
@@ -689,10 +699,12 @@ bool la_wave_ok(int n, int max_len, int n_active) {
 }
 
 hipError_t launch_la_wave(hipStream_t s, const DevArrays& a, int G, int n, const int32_t* c_old, int64_t E, int nts,
-                          int head, int32_t* err, const int32_t* lmap, int na, bool narrow) {
+                          int head, int32_t* err, const int32_t* lmap, int na, bool narrow, const LaSubset& sub) {
     if (nts > 1 && (G != 1 || c_old)) return hipErrorInvalidValue;
-    return a.compact ? la_wave_dispatch<uint16_t>(s, a, G, n, c_old, E, nts, head, err, lmap, na, narrow)
-                     : la_wave_dispatch<int32_t>(s, a, G, n, c_old, E, nts, head, err, lmap, na, narrow);
+    if (sub.count > 0 && (nts < 2 || head > 0 || sub.first < 0 || sub.first + sub.count > nts || !sub.c_lim))
+        return hipErrorInvalidValue;
+    return a.compact ? la_wave_dispatch<uint16_t>(s, a, G, n, c_old, E, nts, head, err, lmap, na, narrow, sub)
+                     : la_wave_dispatch<int32_t>(s, a, G, n, c_old, E, nts, head, err, lmap, na, narrow, sub);
 }
 
 }  // namespace hgx

@@ -862,8 +862,8 @@ class Hashgraph:
                     pending_loaded=self.PendingLoadedEvents(graph), blocks=self.Blocks(graph))
 
     def phase_times(self):
-        out = np.zeros(22, np.float64)
-        self.L.hgx_phase_times(self.ctx, ptr(out), 22)
+        out = np.zeros(23, np.float64)
+        self.L.hgx_phase_times(self.ctx, ptr(out), 23)
         return dict(coords_ms=out[0], rounds_ms=out[1], fame_ms=out[2], order_ms=out[3],
                     la_sweeps=int(out[4]), rounds=int(out[5]), compact=int(out[6]),
                     la_rows=int(out[7]), rebuild=int(out[8]), r_lo=int(out[9]),
@@ -871,7 +871,14 @@ class Hashgraph:
                     round_p_runs=int(out[13]), round_p_fallbacks=int(out[14]), round_p_ovf=int(out[15]),
                     round_p_fail_round=int(out[16]), round_p_fail_chain=int(out[17]),
                     round_g_runs=int(out[18]), la_small=int(out[19]), la_verify=int(out[20]),
-                    sort_seg=int(out[21]))
+                    sort_seg=int(out[21]), ingest_pieces=int(out[22]))
+
+    def set_ingest_pipeline(self, pieces, min_events=4_000_000):
+        """insert_and_run of compact columns on an empty context: the structure columns in `pieces`
+        pieces, each inserted, laid out and its lastAncestors segments started while the next is
+        copied (0: the serial order); batches below min_events stay serial. Same results."""
+        if self.L.hgx_set_ingest_pipeline(self.ctx, int(pieces), int(min_events)) != 0:
+            raise ValueError(f"invalid ingest pipeline {pieces}, {min_events}")
 
     def set_fame_tally(self, mode):
         """DecideFame tally: "popc" (default), "vote" (per-round kernel) or "mfma" (int8 MFMA)."""

@@ -653,6 +653,9 @@ int32_t hgx_p256_verify_bench(int32_t device, const uint8_t* keys65, int32_t n_k
  * DivideRounds calls whose persistent launch gave up and were redone per round, and the
  * candidate rows it counted with exact compares (over 8 bits), the round and chain of the last
  * persistent launch that gave up, then the whole-graph round launches so far (up to 19 values) */
+/* ... 1 if the last DivideRounds ran the whole graph in one workgroup, 1 if its verify sweep ran, the
+ * FindOrders sorted by buckets, and the pieces of the last hgx_insert_and_run32's pipelined ingest
+ * (0: the serial path) (up to 23 values) */
 int32_t hgx_phase_times(hgx_ctx* ctx, double* out, int32_t cap);
 /* dominant-kernel accounting for the roofline line of bench.py:
  * name of the kernel, summed device ms (the round steps time one hipGraph replay in four and
@@ -669,6 +672,14 @@ int32_t hgx_set_coord_storage(hgx_ctx* ctx, int32_t mode);
 /* DecideFame vote tally: 0 = witness-tiled popcount (default), 1 = per-round popcount
  * kernel, 2 = witness-tiled int8 MFMA. Same results; for measurement. */
 int32_t hgx_set_fame_tally(hgx_ctx* ctx, int32_t mode);
+/* hgx_insert_and_run32 on an empty, unrooted, unsharded one-graph context of n <= 896 with at least
+ * min_events events (default 4 000 000) and a time-segmented lastAncestors pass: the structure columns
+ * cross PCIe in `pieces` pieces (default 4, at most 8) and each piece is inserted, laid out and its
+ * segments' lastAncestors started while the later ones are still being copied (on twice the time
+ * segments of a serial rebuild unless hgx_set_la_kernel fixes their number). pieces = 0: always the
+ * serial order. Same results and errors (a failed check redoes the batch serially); for measurement
+ * (DESIGN.md §3.0). */
+int32_t hgx_set_ingest_pipeline(hgx_ctx* ctx, int32_t pieces, int64_t min_events);
 /* DivideRounds lastAncestors: 0 = one dataflow pass per (graph, column block) where it
  * applies (default: n <= 896, chains < 2^21 rows; hgx_la_wave.hip), and for a small graph
  * (n <= 32 compact / 16 int32, its rows within 150 KB) the pass with the whole graph in one
