@@ -78,6 +78,10 @@ struct GraphState {
     std::vector<int8_t> fame;              // [(last_round+1) x n] RoundEvent.Famous (host state)
     std::vector<int32_t> round_events;     // [last_round+1]
     std::vector<Block> blocks;
+    // DecideFame's scratch, kept between calls: the rounds decided in a call and their marks
+    // ([last_round+1], all zero between calls)
+    std::vector<int32_t> dec_list;
+    std::vector<uint8_t> dec_mark;
     void reset() {   // a fresh NewHashgraph's consensus state (keeps allocations)
         undecided.assign(1, 0);
         queued_upto = -1;
@@ -163,7 +167,18 @@ struct hgx_ctx {
     void* gx_out = nullptr;   // FindOrder's timestamp exchange: this shard's values (device memory)
     void* gx_in = nullptr;    // ... another shard's, copied here before the import
     size_t gx_out_cap = 0, gx_in_cap = 0;
+    // host wall clock of the last call's host-only sections (hgx_phase_times): the bookkeeping after
+    // DivideRounds, after DecideFame, around FindOrder's device work, and the payload commit
+    double host_ms[4] = {0, 0, 0, 0};
+    // a fused call (hgx_insert_and_run*, hgx_run_consensus) launched DecideFame's device work from
+    // DivideRounds' bookkeeping; decide_fame_one waits for it instead of launching
+    bool fame_launched = false;
 };
+
+using HostClock = std::chrono::steady_clock;
+static double ms_since(HostClock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(HostClock::now() - t0).count();
+}
 
 static void set_err(hgx_error* err, int32_t code, const std::string& msg) {
     if (!err) return;
@@ -518,6 +533,10 @@ int32_t hgx_insert_events(hgx_ctx* c, const hgx_events* ev, int64_t count, int64
     return insert_events_one(c, ev, count, n_inserted, err);
 }
 
+static int32_t run_after_split(hgx_ctx* c, hgx::InsertOut& out, int64_t* n_inserted, hgx_error* err, const char* who);
+static int32_t divide_rounds_fused(hgx_ctx* c, hgx_error* err, int fuse);
+static int32_t decide_fame_one(hgx_ctx* c, hgx_error* err);
+
 // Bootstrap / Core.Sync + RunConsensus in one call (hashgraph.go:1008-1037, node/core.go:190-303):
 // InsertEvent for the batch, then DivideRounds, DecideFame and FindOrder. The insert is split
 // (Engine::insert_split_begin): the structure columns are validated and committed first, and
@@ -537,37 +556,12 @@ int32_t hgx_insert_and_run(hgx_ctx* c, const hgx_events* ev, int64_t count, int6
         return hgx_run_consensus(c, err);
     }
     DeviceGuard dg(c);
-    const int64_t E0 = c->eng.E;
     hgx::InsertOut out;
     hipError_t e = c->eng.insert_split_begin(ev->creator, ev->index, ev->self_parent, ev->other_parent, count, out);
     if (e != hipSuccess) return dev_err(err, e, "hgx_insert_and_run");
     e = c->eng.payload_begin(ev->timestamp_ns, ev->hash, ev->sig_s, ev->ntx, ev->tx_nil, out.accepted);
     if (e != hipSuccess) return dev_err(err, e, "hgx_insert_and_run");
-    // the per-creator mirrors and UndeterminedEvents now; PendingLoadedEvents once the payload
-    // (IsLoaded) is committed
-    hgx::InsertOut head = out;
-    head.graph_loaded.assign(c->g_loaded.begin(), c->g_loaded.end());
-    hgx_error ins_err{};
-    const int32_t ins_rc = finish_insert(c, head, n_inserted, &ins_err);
-    int32_t rc = ins_rc ? ins_rc : hgx_divide_rounds(c, err);
-    const bool laid_out = ins_rc == 0 && rc == 0;
-    std::vector<uint64_t> loaded;
-    e = c->eng.payload_end(E0, out.accepted, laid_out, c->rh.r_lo, loaded);
-    if (e != hipSuccess) return dev_err(err, e, "hgx_insert_and_run");
-    for (int g = 0; g < c->G; g++) {
-        const int64_t l = (int64_t)loaded[g];
-        c->gs[g].pending_loaded += l - c->g_loaded[g];
-        c->g_loaded[g] = l;
-    }
-    c->mirror_ok = false;
-    if (ins_rc) {   // the accepted prefix is inserted; consensus does not run (as hgx_bootstrap)
-        if (err) *err = ins_err;
-        return ins_rc;
-    }
-    if (rc) return rc;
-    rc = hgx_decide_fame(c, err);
-    if (rc) return rc;
-    return hgx_find_order(c, err);
+    return run_after_split(c, out, n_inserted, err, "hgx_insert_and_run");
 }
 
 static bool bad_events32(const hgx_events32* ev, int64_t count) {
@@ -607,10 +601,10 @@ int32_t hgx_insert_events32(hgx_ctx* c, const hgx_events32* ev, int64_t count, i
     return insert_events32_one(c, ev, count, n_inserted, err);
 }
 
-// the rest of a compact-payload insert_and_run once the structure is committed and the payload copy
-// started (hgx_insert_and_run32 / _packed): DivideRounds beside the copy, then DecideFame, FindOrder
-static int32_t run_after_split32(hgx_ctx* c, int64_t E0, hgx::InsertOut& out, int64_t* n_inserted, hgx_error* err,
-                                 const char* who) {
+// the rest of an insert_and_run once the structure is committed and the payload copy started
+// (hgx_insert_and_run, hgx_insert_and_run32 / _packed): DivideRounds beside the copy, then DecideFame,
+// FindOrder
+static int32_t run_after_split(hgx_ctx* c, hgx::InsertOut& out, int64_t* n_inserted, hgx_error* err, const char* who) {
     hipError_t e;
     // S lands last (FindOrder's sort waits for it); on every way out the caller's S buffer has been
     // read completely
@@ -622,11 +616,23 @@ static int32_t run_after_split32(hgx_ctx* c, int64_t E0, hgx::InsertOut& out, in
     head.graph_loaded.assign(c->g_loaded.begin(), c->g_loaded.end());
     hgx_error ins_err{};
     const int32_t ins_rc = finish_insert(c, head, n_inserted, &ins_err);
-    int32_t rc = ins_rc ? ins_rc : hgx_divide_rounds(c, err);
-    const bool laid_out = ins_rc == 0 && rc == 0;
+    // DivideRounds commits the compact payload's first columns ahead of the rounds; on its way out
+    // it queues the payload's rest and DecideFame's device work, and counts the rounds' events
+    // beside that (divide_rounds_one), so one host round trip serves both
+    int32_t rc = ins_rc ? ins_rc : divide_rounds_fused(c, err, 2);
+    const bool fused = c->fame_launched;
+    if (fused) {
+        rc = decide_fame_one(c, err);
+    } else {
+        // no DivideRounds (a failed insert: the accepted prefix is inserted, the payload committed,
+        // no consensus), a failed one, or a sharded group's: the payload's rest and its own round trip
+        e = c->eng.payload_finish(ins_rc == 0 && rc == 0, c->rh.r_lo);
+        if (e == hipSuccess) e = c->eng.sync();
+        if (e != hipSuccess) return dev_err(err, e, who);
+    }
     std::vector<uint64_t> loaded;
-    e = c->eng.payload_end(E0, out.accepted, laid_out, c->rh.r_lo, loaded);
-    if (e != hipSuccess) return dev_err(err, e, who);
+    c->eng.payload_loaded(loaded);
+    c->host_ms[3] = c->eng.pay_host_ms;
     for (int g = 0; g < c->G; g++) {
         const int64_t l = (int64_t)loaded[g];
         c->gs[g].pending_loaded += l - c->g_loaded[g];
@@ -638,8 +644,10 @@ static int32_t run_after_split32(hgx_ctx* c, int64_t E0, hgx::InsertOut& out, in
         return ins_rc;
     }
     if (rc) return rc;
-    rc = hgx_decide_fame(c, err);
-    if (rc) return rc;
+    if (!fused) {
+        rc = hgx_decide_fame(c, err);
+        if (rc) return rc;
+    }
     rc = hgx_find_order(c, err);
     if (rc) return rc;
     // the S copy's outcome is reported here (FindOrder waits for it only when it sorts; a skipped
@@ -665,19 +673,21 @@ int32_t hgx_insert_and_run32(hgx_ctx* c, const hgx_events32* ev, int64_t count, 
         return hgx_run_consensus(c, err);
     }
     DeviceGuard dg(c);
-    const int64_t E0 = c->eng.E;
     hgx::InsertOut out;
     // a large first batch: inserted, laid out and its lastAncestors started piece by piece while the
     // later columns still cross PCIe; otherwise, or after a failed check, as before
     bool piped = false;
     hipError_t e = c->grp ? hipSuccess
-                          : c->eng.insert_pipe32(ev->creator, ev->index, ev->self_parent, ev->other_parent, count, out, piped);
+                          : c->eng.insert_pipe32(ev->creator, ev->index, ev->self_parent, ev->other_parent,
+                                                 ev->timestamp_ns, ev->coin, ev->sig_s, ev->ntx, count, out, piped);
     if (e != hipSuccess) return dev_err(err, e, "hgx_insert_and_run32");
-    if (!piped) e = c->eng.insert_split_begin32(ev->creator, ev->index, ev->self_parent, ev->other_parent, count, out);
-    if (e != hipSuccess) return dev_err(err, e, "hgx_insert_and_run32");
-    e = c->eng.payload_begin32(ev->timestamp_ns, ev->coin, ev->sig_s, ev->ntx, out.accepted);
-    if (e != hipSuccess) return dev_err(err, e, "hgx_insert_and_run32");
-    return run_after_split32(c, E0, out, n_inserted, err, "hgx_insert_and_run32");
+    if (!piped) {   // (the pipeline's copier goes on with the payload itself)
+        e = c->eng.insert_split_begin32(ev->creator, ev->index, ev->self_parent, ev->other_parent, count, out);
+        if (e != hipSuccess) return dev_err(err, e, "hgx_insert_and_run32");
+        e = c->eng.payload_begin32(ev->timestamp_ns, ev->coin, ev->sig_s, ev->ntx, out.accepted);
+        if (e != hipSuccess) return dev_err(err, e, "hgx_insert_and_run32");
+    }
+    return run_after_split(c, out, n_inserted, err, "hgx_insert_and_run32");
 }
 
 // ---- hgx_events_packed (include/hgx.h): 10-byte structure columns, decoded on the device ----
@@ -748,13 +758,12 @@ int32_t hgx_insert_and_run_packed(hgx_ctx* c, const hgx_events_packed* ev, int64
         return hgx_run_consensus(c, err);
     }
     DeviceGuard dg(c);
-    const int64_t E0 = c->eng.E;
     hgx::InsertOut out;
     hipError_t e = c->eng.insert_split_begin_packed(packed_of(ev), count, out);
     if (e != hipSuccess) return dev_err(err, e, "hgx_insert_and_run_packed");
     e = c->eng.payload_begin32(ev->timestamp_ns, ev->coin, ev->sig_s, ev->ntx, out.accepted);
     if (e != hipSuccess) return dev_err(err, e, "hgx_insert_and_run_packed");
-    return run_after_split32(c, E0, out, n_inserted, err, "hgx_insert_and_run_packed");
+    return run_after_split(c, out, n_inserted, err, "hgx_insert_and_run_packed");
 }
 
 int32_t hgx_pack_events32(const hgx_events32* ev, int64_t count, int64_t base, uint16_t* creator16, uint16_t* sp_back,
@@ -1831,40 +1840,84 @@ int32_t hgx_set_root_ids(hgx_ctx* c, const uint8_t* x_id32, const int32_t* has_x
 }
 
 // ---- DivideRounds (hashgraph.go:616-646) -----------------------------------------
-static int32_t divide_rounds_one(hgx_ctx* c, hgx_error* err) {
+// the first round DecideFame's device pass has to look at: decided fame is never revisited, so
+// only rounds from the first undecided one
+static int32_t fame_first_round(const hgx_ctx* c) {
+    int32_t f0 = c->rh.R;
+    for (int g = 0; g < c->G; g++)
+        for (int32_t r : c->gs[g].undecided)
+            if (r >= 0 && r <= c->gs[g].last_round) f0 = std::min(f0, r);
+    return f0;
+}
+
+// RoundInfo's event counts of rounds [r_lo, LR] from the chains' round boundaries: O(R C), one
+// pass over the rows of rh.bm (each row summed once)
+static void count_round_events(hgx_ctx* c, int g) {
+    GraphState& s = c->gs[g];
+    const int C = c->C, n = c->n;
+    const int32_t LR = s.last_round;
+    // rounds below r_lo kept their boundaries (incremental DivideRounds)
+    const int32_t r_a = std::min(c->rh.r_lo, LR + 1);
+    if (r_a > LR) return;
+    auto row_sum = [&](int32_t r) {
+        const int32_t* row = c->rh.bm.data() + (size_t)r * C + (size_t)g * n;
+        int64_t sum = 0;
+        for (int cl = 0; cl < n; cl++) sum += row[cl];
+        return sum;
+    };
+    int64_t lo = row_sum(r_a);
+    for (int32_t r = r_a; r <= LR; r++) {
+        const int64_t hi = row_sum(r + 1);
+        s.round_events[r] = (int32_t)(hi - lo);
+        lo = hi;
+    }
+}
+
+// fuse (the calls that go on to DecideFame: hgx_insert_and_run*, hgx_run_consensus): once the
+// undecided queues are known (O(new rounds)), DecideFame's device work is launched -- after the
+// rest of an insert's payload (fuse = 2) -- and the O(R C) event counts run beside it;
+// decide_fame_one then waits for the launch (c->fame_launched). A rooted context queues its rounds by
+// their event counts and a device round trip, and keeps the order without the overlap.
+static int32_t divide_rounds_one(hgx_ctx* c, hgx_error* err, int fuse = 0) {
     if (!c) { set_err(err, HGX_ERR_INVALID, "null context"); return HGX_ERR_INVALID; }
     if (c->divided && c->E_div == c->E) return ok(err);   // nothing new: AddEvent is idempotent
     DeviceGuard dg(c);
     const bool fo_valid = c->fo_prev_valid;
     c->fo_prev_valid = false;   // (until the call completes; a rebuild starts over)
+    // (a fused call takes the round tables' rows out of the staging beside DecideFame's device pass)
+    c->eng.defer_rows = fuse && !c->rooted;
     hipError_t e = c->eng.divide_rounds(c->E, c->chain_len, c->chain_base, c->rh);
+    c->eng.defer_rows = false;
     if (e != hipSuccess) return dev_err(err, e, "hgx_divide_rounds");
+    const HostClock::time_point t_host = HostClock::now();
     const bool keep_fo = fo_valid && !c->eng.last_rebuild;
     c->divided = true;
     c->E_div = c->E;
     c->rounds_cached = false;
-    const int C = c->C, n = c->n;
+    const int n = c->n;
     for (int g = 0; g < c->G; g++) {
         GraphState& s = c->gs[g];
         const int32_t LR = c->rh.last_round[g];
         s.last_round = LR;
         s.fame.resize((size_t)(LR + 1) * n, 0);
-        // rounds below r_lo kept their boundaries (incremental DivideRounds)
         s.round_events.resize(LR + 1, 0);
-        for (int32_t r = std::min(c->rh.r_lo, LR + 1); r <= LR; r++) {
-            int64_t cnt = 0;
-            for (int cl = 0; cl < n; cl++) {
-                const int gc = g * n + cl;
-                cnt += c->rh.bm[(size_t)(r + 1) * C + gc] - c->rh.bm[(size_t)r * C + gc];
-            }
-            s.round_events[r] = (int32_t)cnt;
-        }
-        if (!c->rooted) {
-            // rounds first seen in this call are queued in ascending order
-            for (int32_t r = s.queued_upto + 1; r <= LR; r++) s.undecided.push_back(r);
-            s.queued_upto = std::max(s.queued_upto, LR);
-            continue;
-        }
+        if (c->rooted) continue;
+        // rounds first seen in this call are queued in ascending order
+        for (int32_t r = s.queued_upto + 1; r <= LR; r++) s.undecided.push_back(r);
+        s.queued_upto = std::max(s.queued_upto, LR);
+    }
+    if (fuse && !c->rooted) {
+        if (fuse == 2) e = c->eng.payload_finish(true, c->rh.r_lo);
+        if (e == hipSuccess) e = c->eng.decide_fame_launch(fame_first_round(c), c->fame_dev);
+        c->fame_launched = e == hipSuccess;
+    }
+    c->eng.divide_rounds_rows(c->rh);
+    if (e != hipSuccess) return dev_err(err, e, "hgx_decide_fame");
+    for (int g = 0; g < c->G; g++) {
+        GraphState& s = c->gs[g];
+        const int32_t LR = s.last_round;
+        count_round_events(c, g);
+        if (!c->rooted) continue;
         // after a Reset rounds start at the roots' rounds and can first appear out of order:
         // queue the rounds with events not queued yet by their first event (DivideRounds
         // walks UndeterminedEvents in insertion order, hashgraph.go:617-638)
@@ -1883,6 +1936,7 @@ static int32_t divide_rounds_one(hgx_ctx* c, hgx_error* err) {
         s.queued_upto = std::max(s.queued_upto, LR);
     }
     c->fo_prev_valid = keep_fo;
+    c->host_ms[0] = ms_since(t_host);
     return ok(err);
 }
 
@@ -1893,17 +1947,15 @@ int32_t hgx_divide_rounds(hgx_ctx* c, hgx_error* err) {
     return divide_rounds_one(c, err);
 }
 
-static bool is_witness(const hgx_ctx* c, int32_t r, int gc) {
-    return r >= 0 && r < c->rh.R && c->rh.wflag[(size_t)r * c->C + gc] == 2;
+// DivideRounds of a call that goes on to DecideFame (divide_rounds_one's fuse); a sharded group
+// keeps the separate calls
+static int32_t divide_rounds_fused(hgx_ctx* c, hgx_error* err, int fuse) {
+    if (c && c->grp) return hgx_divide_rounds(c, err);
+    return divide_rounds_one(c, err, fuse);
 }
 
-// RoundInfo.WitnessesDecided (roundInfo.go:64-71); rounds never stored are vacuously decided
-static bool witnesses_decided(const hgx_ctx* c, int g, int32_t r) {
-    const GraphState& s = c->gs[g];
-    if (r < 0 || r > s.last_round) return true;
-    for (int cl = 0; cl < c->n; cl++)
-        if (is_witness(c, r, g * c->n + cl) && s.fame[(size_t)r * c->n + cl] == 0) return false;
-    return true;
+static bool is_witness(const hgx_ctx* c, int32_t r, int gc) {
+    return r >= 0 && r < c->rh.R && c->rh.wflag[(size_t)r * c->C + gc] == 2;
 }
 
 // ---- DecideFame (hashgraph.go:649-750) -------------------------------------------
@@ -1911,34 +1963,45 @@ static int32_t decide_fame_one(hgx_ctx* c, hgx_error* err) {
     if (!c) { set_err(err, HGX_ERR_INVALID, "null context"); return HGX_ERR_INVALID; }
     DeviceGuard dg(c);
     std::vector<int8_t>& dev = c->fame_dev;   // kept between calls (rows below the first undecided one unused)
-    if (c->divided) {
-        // decided fame is never revisited: only rounds from the first undecided one
-        int32_t f0 = c->rh.R;
-        for (int g = 0; g < c->G; g++)
-            for (int32_t r : c->gs[g].undecided)
-                if (r >= 0 && r <= c->gs[g].last_round) f0 = std::min(f0, r);
-        hipError_t e = c->eng.decide_fame(f0, dev);
+    if (c->fame_launched) {   // a fused call's DivideRounds launched the device pass
+        c->fame_launched = false;
+        hipError_t e = c->eng.decide_fame_wait();
+        if (e != hipSuccess) return dev_err(err, e, "hgx_decide_fame");
+    } else if (c->divided) {
+        hipError_t e = c->eng.decide_fame(fame_first_round(c), dev);
         if (e != hipSuccess) return dev_err(err, e, "hgx_decide_fame");
     }
+    const HostClock::time_point t_host = HostClock::now();
     int32_t rc = HGX_OK;
     std::string msg;
     const int n = c->n, C = c->C;
     for (int g = 0; g < c->G; g++) {
         GraphState& s = c->gs[g];
-        std::vector<int32_t> decided;
+        std::vector<int32_t>& decided = s.dec_list;
+        decided.clear();
         for (size_t pos = 0; pos < s.undecided.size(); pos++) {
             const int32_t i = s.undecided[pos];
             if (i < 0 || i > s.last_round) {          // Store.GetRound miss -> error
                 if (rc == HGX_OK) { rc = HGX_ERR_KEY_NOT_FOUND; msg = std::to_string(i) + ", Not Found"; }
                 break;
             }
+            // one pass over the round's rows (i <= last_round < rh.R): SetFame for the witnesses not
+            // decided yet (decided fame is never revisited) and RoundInfo.WitnessesDecided
+            // (roundInfo.go:64-71) of the merged row
+            // (byte masks instead of branches, and rows that do not alias: the loop vectorizes)
+            const uint8_t* __restrict ws = c->rh.wflag.data() + (size_t)i * C + (size_t)g * n;
+            const uint8_t* __restrict dv = (const uint8_t*)dev.data() + (size_t)i * C + (size_t)g * n;
+            uint8_t* __restrict fm = (uint8_t*)s.fame.data() + (size_t)i * n;
+            uint8_t open = 0;
             for (int cl = 0; cl < n; cl++) {
-                const int gc = g * n + cl;
-                if (!is_witness(c, i, gc)) continue;
-                int8_t& f = s.fame[(size_t)i * n + cl];
-                if (f == 0) f = dev[(size_t)i * C + gc];   // SetFame; decided fame is never revisited
+                const uint8_t w = (uint8_t)-(ws[cl] == 2);             // 0xFF: a witness
+                const uint8_t f = fm[cl];
+                const uint8_t take = (uint8_t)(w & (uint8_t)-(f == 0));   // 0xFF: take the device's value
+                const uint8_t m = (uint8_t)((dv[cl] & take) | (f & (uint8_t)~take));
+                fm[cl] = m;
+                open |= (uint8_t)(w & (uint8_t)-(m == 0));
             }
-            if (witnesses_decided(c, g, i)) {
+            if (!open) {
                 decided.push_back(i);
                 if (!s.has_lcr || i > s.lcr) {             // setLastConsensusRound (:743-750)
                     s.has_lcr = true;
@@ -1948,14 +2011,16 @@ static int32_t decide_fame_one(hgx_ctx* c, hgx_error* err) {
             }
         }
         // deferred updateUndecidedRounds (:733-741): drop every copy of a decided round
-        std::vector<uint8_t> is_dec((size_t)std::max(0, s.last_round) + 1, 0);
-        for (int32_t r : decided) is_dec[(size_t)r] = 1;
-        std::vector<int32_t> keep;
-        keep.reserve(s.undecided.size());
+        if (decided.empty()) continue;
+        if (s.dec_mark.size() < (size_t)s.last_round + 1) s.dec_mark.resize((size_t)s.last_round + 1, 0);
+        for (int32_t r : decided) s.dec_mark[(size_t)r] = 1;
+        size_t kept = 0;
         for (int32_t r : s.undecided)
-            if (r < 0 || r > s.last_round || !is_dec[(size_t)r]) keep.push_back(r);
-        s.undecided.swap(keep);
+            if (r < 0 || r > s.last_round || !s.dec_mark[(size_t)r]) s.undecided[kept++] = r;
+        s.undecided.resize(kept);
+        for (int32_t r : decided) s.dec_mark[(size_t)r] = 0;
     }
+    c->host_ms[1] = ms_since(t_host);
     if (rc != HGX_OK) { set_err(err, rc, msg); return rc; }
     return ok(err);
 }
@@ -1965,6 +2030,15 @@ int32_t hgx_decide_fame(hgx_ctx* c, hgx_error* err) {
     return decide_fame_one(c, err);
 }
 
+// one round's famous-witness flags from its witness flags and fame (byte masks, rows that do not
+// alias: the loop vectorizes); returns non-zero when a witness is undecided
+static uint8_t famous_row(const uint8_t* __restrict ws, const uint8_t* __restrict fm, uint8_t* __restrict fwr, int n) {
+    for (int cl = 0; cl < n; cl++) fwr[cl] = (uint8_t)((ws[cl] == 2) & (fm[cl] == 1));
+    unsigned open = 0;
+    for (int cl = 0; cl < n; cl++) open |= (unsigned)((ws[cl] == 2) & (fm[cl] == 0));
+    return (uint8_t)open;
+}
+
 // ---- FindOrder (hashgraph.go:801-858) --------------------------------------------
 // In two halves: begin = DecideRoundReceived and the consensus timestamps of this context's
 // shard of chains (all chains unless hgx_set_shard); end = the ConsensusSorter order and the
@@ -1972,7 +2046,9 @@ int32_t hgx_decide_fame(hgx_ctx* c, hgx_error* err) {
 static int32_t find_order_begin_one(hgx_ctx* c, hgx_error* err) {
     if (!c) { set_err(err, HGX_ERR_INVALID, "null context"); return HGX_ERR_INVALID; }
     c->fo_open = false;
+    c->host_ms[2] = 0;
     if (!c->divided) return ok(err);
+    const HostClock::time_point t_host = HostClock::now();
     DeviceGuard dg(c);
     const int n = c->n, C = c->C, G = c->G;
     const int32_t R = c->rh.R;
@@ -1998,28 +2074,26 @@ static int32_t find_order_begin_one(hgx_ctx* c, hgx_error* err) {
     std::vector<uint8_t> ure(G, 0);
     elig.assign((size_t)G * std::max(R, 1), 0);
     if (fw.size() < (size_t)std::max(R, 1) * C) fw.resize((size_t)std::max(R, 1) * C, 0);
-    if (R > std::max(r0, 0))
-        std::memset(fw.data() + (size_t)std::max(r0, 0) * C, 0, (size_t)(R - std::max(r0, 0)) * C);
     for (int g = 0; g < G; g++) {
         const GraphState& s = c->gs[g];
         ure[g] = s.undecided.empty() ? 1 : 0;
         const int32_t U0 = s.undecided.empty() ? -1 : s.undecided[0];
-        for (int32_t i = std::max(r0, 0); i <= s.last_round; i++) {
-            // one pass over the round's chains: famous witnesses, and WitnessesDecided
-            // (roundInfo.go:64-71) for the DecideRoundReceived skip rule (hashgraph.go:763)
-            bool decided = true;
-            const uint8_t* ws = c->rh.wflag.data() + (size_t)i * C + (size_t)g * n;
-            const int8_t* fm = s.fame.data() + (size_t)i * n;
-            uint8_t* fwr = fw.data() + (size_t)i * C + (size_t)g * n;
-            for (int cl = 0; cl < n; cl++) {
-                if (ws[cl] != 2) continue;
-                if (fm[cl] == 0) decided = false;
-                if (fm[cl] == 1) fwr[cl] = 1;
-            }
-            elig[(size_t)g * R + i] = (U0 >= 0 && i < U0 && decided) ? 1 : 0;
+        const int32_t i0 = std::max(r0, 0);
+        for (int32_t i = i0; i <= s.last_round; i++) {
+            // one pass over the round's chains, every flag of the row written (no clear before it):
+            // famous witnesses, and WitnessesDecided (roundInfo.go:64-71) for the DecideRoundReceived
+            // skip rule (hashgraph.go:763)
+            const uint8_t open = famous_row(c->rh.wflag.data() + (size_t)i * C + (size_t)g * n,
+                                            (const uint8_t*)s.fame.data() + (size_t)i * n,
+                                            fw.data() + (size_t)i * C + (size_t)g * n, n);
+            elig[(size_t)g * R + i] = (U0 >= 0 && i < U0 && !open) ? 1 : 0;
         }
+        // (the rows of the rounds this graph has not reached: no witnesses)
+        for (int32_t i = std::max(i0, s.last_round + 1); i < R; i++)
+            std::memset(fw.data() + (size_t)i * C + (size_t)g * n, 0, (size_t)n);
     }
     hgx::OrderHost& oh = c->fo;
+    c->host_ms[2] = ms_since(t_host);
     hipError_t e = c->eng.find_order_begin(elig, fw, ure, r0, max_unrecv, oh);
     if (e != hipSuccess) return dev_err(err, e, "hgx_find_order");
     if (oh.panic) {
@@ -2061,6 +2135,7 @@ static int32_t find_order_end_one(hgx_ctx* c, hgx_error* err) {
     }
     hipError_t e = c->eng.find_order_end(oh, pre);
     if (e != hipSuccess) return dev_err(err, e, "hgx_find_order");
+    const HostClock::time_point t_host = HostClock::now();
     c->recv_cached = false;
     // the device order is graph-major: one D2H copy appends it to the arena and every
     // graph gets its segment
@@ -2124,6 +2199,7 @@ static int32_t find_order_end_one(hgx_ctx* c, hgx_error* err) {
     c->fo_prev_u0.swap(c->fo_pend_u0);   // the order is committed: the skip rule may use it
     c->fo_prev_valid = c->fo_pend_valid;
     c->fo_pend_valid = false;
+    c->host_ms[2] += ms_since(t_host);
     for (const auto& gb : commits) {   // commitCh <- block, in SetBlock order
         const Block& b = c->gs[gb.first].blocks[(size_t)gb.second];
         c->commit_fn(c->commit_user, gb.first, gb.second, b.rr, b.first, b.nev, b.ntx);
@@ -2257,7 +2333,7 @@ int32_t hgx_shard_import(hgx_ctx* c, int32_t src_rank, const void* src, int32_t 
 }
 
 int32_t hgx_run_consensus(hgx_ctx* c, hgx_error* err) {
-    int32_t rc = hgx_divide_rounds(c, err);
+    int32_t rc = divide_rounds_fused(c, err, 1);   // (DecideFame's device work launched from its bookkeeping)
     if (rc) return rc;
     rc = hgx_decide_fame(c, err);
     if (rc) return rc;
@@ -2692,8 +2768,8 @@ int32_t hgx_witness(hgx_ctx* c, int64_t x) {
 // ---- instrumentation / knobs ----------------------------------------------------------
 int32_t hgx_phase_times(hgx_ctx* c, double* out, int32_t cap) {
     if (!c || !out) return 0;
-    const int32_t m = std::min<int32_t>(cap, 23);
-    double v[23] = {c->eng.phase_ms[0], c->eng.phase_ms[1], c->eng.phase_ms[2], c->eng.phase_ms[3],
+    const int32_t m = std::min<int32_t>(cap, 27);
+    double v[27] = {c->eng.phase_ms[0], c->eng.phase_ms[1], c->eng.phase_ms[2], c->eng.phase_ms[3],
                     (double)c->eng.la_sweeps, (double)c->eng.R, (double)c->eng.compact,
                     (double)c->eng.la_rows, c->eng.last_rebuild ? 1.0 : 0.0, (double)c->rh.r_lo,
                     c->eng.la_wave_used ? 1.0 : 0.0, (double)c->eng.la_wave_fallbacks,
@@ -2701,7 +2777,8 @@ int32_t hgx_phase_times(hgx_ctx* c, double* out, int32_t cap) {
                     (double)c->eng.round_p_fallbacks, (double)c->eng.round_p_ovf,
                     (double)c->eng.round_p_fail_round, (double)c->eng.round_p_fail_chain,
                     (double)c->eng.round_g_runs, c->eng.la_small_used ? 1.0 : 0.0,
-                    c->eng.la_verified ? 1.0 : 0.0, (double)c->eng.sort_seg_runs, (double)c->eng.pipe_used};
+                    c->eng.la_verified ? 1.0 : 0.0, (double)c->eng.sort_seg_runs, (double)c->eng.pipe_used,
+                    c->host_ms[0], c->host_ms[1], c->host_ms[2], c->host_ms[3]};
     for (int32_t i = 0; i < m; i++) out[i] = v[i];
     return m;
 }

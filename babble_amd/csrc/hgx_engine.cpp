@@ -707,6 +707,10 @@ hipError_t Engine::payload_begin32(const int64_t* ts, const uint8_t* coin, const
     pay32 = true;
     pay_stage = 0;
     pay_S_pending = true;
+    pay_commit_pending = true;
+    pay_E0 = E - m_ok;
+    pay_m = m_ok;
+    pay_host_ms = 0;
     if (m_ok > 0) ids_known = false;
     uint8_t* S_dst = g_S.p + 32 * (size_t)(E - m_ok);   // the accepted prefix (just appended): gids E - m_ok ..
     pay_thread = std::thread([=]() {
@@ -741,6 +745,10 @@ hipError_t Engine::payload_begin(const int64_t* ts, const uint8_t* hash, const u
     pay_err = hipSuccess;
     pay32 = false;
     pay_S_pending = false;
+    pay_commit_pending = true;
+    pay_E0 = E - m_ok;
+    pay_m = m_ok;
+    pay_host_ms = 0;
     // pageable host memory: each copy returns once its source has been consumed, so the copies
     // run on their own host thread (and stream) beside the DivideRounds launches
     pay_thread = std::thread([=]() {
@@ -757,8 +765,20 @@ hipError_t Engine::payload_begin(const int64_t* ts, const uint8_t* hash, const u
     return hipSuccess;
 }
 
-hipError_t Engine::payload_end(int64_t E0, int64_t m_ok, bool laid_out_new, int32_t wcoin_r0,
-                               std::vector<uint64_t>& loaded) {
+namespace {
+struct HostTimer {   // adds the scope's host wall clock to a counter
+    double& acc;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    explicit HostTimer(double& a) : acc(a) {}
+    ~HostTimer() { acc += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+}  // namespace
+
+hipError_t Engine::payload_commit(bool positions, hipStream_t on) {
+    if (!on) on = stream;
+    if (!pay_commit_pending) return hipSuccess;
+    HostTimer tm(pay_host_ms);
+    pay_commit_pending = false;
     if (pay_S_pending) {   // the compact payload: its first stage only (S lands in g_S later)
         while (pay_stage.load(std::memory_order_acquire) == 0) std::this_thread::yield();
         HGX_TRY(pay_err_a);
@@ -766,7 +786,7 @@ hipError_t Engine::payload_end(int64_t E0, int64_t m_ok, bool laid_out_new, int3
         if (pay_thread.joinable()) pay_thread.join();
         HGX_TRY(pay_err);
     }
-    HGX_TRY(hipStreamWaitEvent(stream, ev_pay, 0));
+    HGX_TRY(hipStreamWaitEvent(on, ev_pay, 0));
     InsertIn in{};
     in.creator = st_creator.p; in.ts = st_ts.p; in.S = pay_S_pending ? nullptr : st_S.p; in.ntx = st_ntx.p;
     if (split32) { in.index32 = st_index32.p; in.sp32 = st_sp32.p; in.op32 = st_op32.p; }
@@ -774,17 +794,27 @@ hipError_t Engine::payload_end(int64_t E0, int64_t m_ok, bool laid_out_new, int3
     if (pay32) in.coin = st_coin.p;
     else { in.hash = st_hash.p; in.nil = st_nil.p; }
     split32 = false;
-    launch_insert_commit(stream, m_ok, nullptr, nullptr, E0, n, in, insert_state(), kCommitPayload);
-    if (laid_out_new) {   // the layout ran before the timestamps and coins were committed
-        launch_ts_to_pos(stream, E0, m_ok, g_pos.p, g_ts.p, p_ts.p);
-        if (R > wcoin_r0) launch_wcoin(stream, arrays(), wcoin_r0, R, C);
+    launch_insert_commit(on, pay_m, nullptr, nullptr, pay_E0, n, in, insert_state(), kCommitPayload);
+    // (the layout ran before the timestamps were committed)
+    if (positions) launch_ts_to_pos(on, pay_E0, pay_m, g_pos.p, g_ts.p, p_ts.p);
+    return hipGetLastError();
+}
+
+hipError_t Engine::payload_finish(bool laid_out_new, int32_t wcoin_r0) {
+    if (pay_commit_pending) {
+        HGX_TRY(payload_commit(laid_out_new));
+        HostTimer tm(pay_host_ms);
+        // the rounds' coin pass read the coins before they were committed
+        if (laid_out_new && R > wcoin_r0) launch_wcoin(stream, arrays(), wcoin_r0, R, C);
+        HGX_TRY(hipGetLastError());
     }
-    HGX_TRY(hipGetLastError());
-    HGX_TRY(hipMemcpyAsync(h_ins, ins_blk.p, ins_blk.n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    HGX_TRY(hipStreamSynchronize(stream));
+    HostTimer tm(pay_host_ms);
+    return hipMemcpyAsync(h_ins, ins_blk.p, ins_blk.n * sizeof(int32_t), hipMemcpyDeviceToHost, stream);
+}
+
+void Engine::payload_loaded(std::vector<uint64_t>& loaded) const {
     loaded.resize(G);
     std::memcpy(loaded.data(), h_ins + ins_gl_off, (size_t)G * 8);
-    return hipSuccess;
 }
 
 hipError_t Engine::payload_wait_S() {
@@ -872,6 +902,7 @@ hipError_t Engine::clear() {
 
 // ---- the pipelined ingest --------------------------------------------------
 hipError_t Engine::insert_pipe32(const int32_t* creator, const int32_t* index, const int32_t* sp, const int32_t* op,
+                                 const int64_t* ts, const uint8_t* coin, const uint8_t* S, const int32_t* ntx,
                                  int64_t count, InsertOut& out, bool& taken) {
     taken = false;
     pipe_used = 0;
@@ -903,12 +934,16 @@ hipError_t Engine::insert_pipe32(const int32_t* creator, const int32_t* index, c
     if (st_index32.n < c) HGX_TRY(st_index32.alloc(c));
     if (st_sp32.n < c) HGX_TRY(st_sp32.alloc(c));
     if (st_op32.n < c) HGX_TRY(st_op32.alloc(c));
+    if (st_ts.n < c) HGX_TRY(st_ts.alloc(c));
+    if (st_coin.n < c) HGX_TRY(st_coin.alloc(c));
+    if (st_ntx.n < c) HGX_TRY(st_ntx.alloc(c));
     const size_t o_hist = 64, o_lim = o_hist + kPipeMaxPieces * Cz;
     if (pipe_buf.n < o_lim + kPipeMaxPieces * Cz) HGX_TRY(pipe_buf.alloc(o_lim + kPipeMaxPieces * Cz));
     if (!stream2) {
         HGX_TRY(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));
         HGX_TRY(hipEventCreateWithFlags(&ev_pay, hipEventDisableTiming));
     }
+    if (!ev_pay_S) HGX_TRY(hipEventCreateWithFlags(&ev_pay_S, hipEventDisableTiming));
     if (!stream_o) {
         HGX_TRY(hipStreamCreateWithFlags(&stream_o, hipStreamNonBlocking));
         for (int k = 0; k <= kOrderParts; k++) HGX_TRY(hipEventCreateWithFlags(&ev_o[k], hipEventDisableTiming));
@@ -925,9 +960,15 @@ hipError_t Engine::insert_pipe32(const int32_t* creator, const int32_t* index, c
     pipe_err = hipSuccess;
     pipe_stage = 0;
     pipe_stop = 0;
+    pay_err = pay_err_a = hipSuccess;
+    pay_stage = 0;
     // one copier: the creator column, then index / sp / op piece by piece, an event behind each
-    // (a host thread: a copy from pageable memory returns only once its source has been consumed)
+    // (a host thread: a copy from pageable memory returns only once its source has been consumed),
+    // then the payload as payload_begin32's copier: ts / coin / ntx and ev_pay, S into g_S (the
+    // context is empty: gid 0) and ev_pay_S. pipe_stop (a way out of the pipeline) ends it at the
+    // next column; what it wrote by then the serial path's own payload copy overwrites.
     std::vector<int64_t> cuts(cut, cut + pieces + 1);
+    uint8_t* S_dst = g_S.p;
     pipe_thread = std::thread([=]() {
         hipError_t e = hipSetDevice(dev);
         if (e == hipSuccess) e = hipMemcpyAsync(st_creator.p, creator, c * 4, hipMemcpyHostToDevice, stream2);
@@ -944,8 +985,19 @@ hipError_t Engine::insert_pipe32(const int32_t* creator, const int32_t* index, c
             if (e != hipSuccess) pipe_err = e;
             pipe_stage.store(k + 2, std::memory_order_release);
         }
+        auto go = [&]() { return e == hipSuccess && !pipe_stop.load(std::memory_order_acquire); };
+        hipError_t ep = e;   // the payload's copies (pay_err_a / pay_err, read once the pipeline was taken)
+        if (go()) ep = hipMemcpyAsync(st_ts.p, ts, c * 8, hipMemcpyHostToDevice, stream2);
+        if (ep == hipSuccess && go()) ep = hipMemcpyAsync(st_coin.p, coin, c, hipMemcpyHostToDevice, stream2);
+        if (ep == hipSuccess && go()) ep = hipMemcpyAsync(st_ntx.p, ntx, c * 4, hipMemcpyHostToDevice, stream2);
+        if (ep == hipSuccess) ep = hipEventRecord(ev_pay, stream2);
+        pay_err_a = ep;
+        pay_stage.store(1, std::memory_order_release);
+        if (ep == hipSuccess && go()) ep = hipMemcpyAsync(S_dst, S, c * 32, hipMemcpyHostToDevice, stream2);
+        if (ep == hipSuccess) ep = hipEventRecord(ev_pay_S, stream2);
         const hipError_t es = hipStreamSynchronize(stream2);   // the caller's columns are read completely
         if (e == hipSuccess && es != hipSuccess) pipe_err = es;
+        pay_err = ep != hipSuccess ? ep : es;
     });
     // every way out joins the copier; `fail` leaves the context empty for the serial path
     auto stop = [&](hipError_t e) {
@@ -1029,17 +1081,27 @@ hipError_t Engine::insert_pipe32(const int32_t* creator, const int32_t* index, c
     PIPE_TRY(copy_to_pinned(h_small, ins_fail.p, 8, 0xFF));
     PIPE_TRY(copy_to_pinned(h_ins, ins_blk.p, ins_blk.n * sizeof(int32_t)));
     PIPE_TRY(stage_issue());
-    PIPE_TRY(hipStreamSynchronize(stream));
-    PIPE_TRY(stop(hipSuccess));
+    PIPE_TRY(hipStreamSynchronize(stream));   // (behind every piece's event: the structure columns are read completely)
 #undef PIPE_TRY
     unsigned long long fail = 0;
     std::memcpy(&fail, h_small, 8);
     if (fail != ~0ull) {
-        // a check failed in some piece: empty the context again (the claims of every piece issued
-        // so far included) and let the serial path produce the error and the accepted prefix
+        // a check failed in some piece: stop the copier, empty the context again (the claims of every
+        // piece issued so far included) and let the serial path produce the error and the accepted
+        // prefix, and copy the payload itself
+        HGX_TRY(stop(hipSuccess));
         E = count;
         return clear();
     }
+    // the copier runs on as the payload's: payload_commit and payload_wait_S find it as payload_begin32's
+    pay_thread = std::move(pipe_thread);
+    pay32 = true;
+    pay_S_pending = true;
+    pay_commit_pending = true;
+    pay_E0 = 0;
+    pay_m = count;
+    pay_host_ms = 0;
+    ids_known = false;
     E = count;
     split32 = true;
     out = InsertOut();
@@ -1646,6 +1708,20 @@ hipError_t Engine::divide_rounds(int64_t En, const std::vector<int32_t>& chain_l
     } else {
         HGX_TRY(run_sweeps(1));
     }
+    // the compact payload of hgx_insert_and_run32 / _packed: its first columns started with this call
+    // (or right behind the pipelined ingest's last piece) and have crossed PCIe under lastAncestors,
+    // so they are committed here, ahead of the rounds and their coin pass, and nothing of the payload
+    // is left between the recurrence and DecideFame. (Not earlier: issuing a copy from pageable memory
+    // returns only once its source is consumed, and the wait for that would hold up the launches above.)
+    // After a pipelined ingest its second side stream is idle (its segments were joined before the
+    // ingest returned, and so was the layout): the commit runs there beside k_fd_build, which neither
+    // reads nor writes what it touches, and the context stream takes it up again before the rounds.
+    bool side_commit = false;
+    if (pay_commit_pending && pay_S_pending && !grp) {
+        side_commit = piped && stream_p != nullptr && time_mask == 0;
+        HGX_TRY(payload_commit(true, side_commit ? stream_p : stream));
+        if (side_commit) HGX_TRY(hipEventRecord(ev_side[1], stream_p));
+    }
     kbeg(K_FD_BUILD);
     if (grp) {   // a chain-sharded group (one graph): the firstDescendants of this shard's chains' events
         launch_fd_build(stream, a, C, n, max_len, fd_ld, cold, max_new, grp->c_split[shard], grp->c_split[shard + 1]);
@@ -1653,6 +1729,7 @@ hipError_t Engine::divide_rounds(int64_t En, const std::vector<int32_t>& chain_l
         launch_fd_build(stream, a, C, n, max_len, fd_ld, cold, max_new);
     }
     kend(K_FD_BUILD, (double)(En - E0) * 2.0 * csz * n);
+    if (side_commit) HGX_TRY(hipStreamWaitEvent(stream, ev_side[1], 0));
     if (rooted) {   // root floors of every position (after a Reset)
         if (gfl.n < (size_t)Ppos) HGX_TRY(gfl.alloc((size_t)Ppos));
         const size_t need = (size_t)(root_gmax + 1) * C;
@@ -2028,7 +2105,17 @@ hipError_t Engine::divide_rounds(int64_t En, const std::vector<int32_t>& chain_l
         la_kernel = keep;
         return re;
     }
-    stage_flush();
+    // the staged rows: the graphs' last rounds (the first entry) are needed now; the boundary and
+    // witness-flag rows (megabytes at c3) can wait for divide_rounds_rows when the caller asked so
+    const bool defer = defer_rows && !stage_out.empty();
+    defer_rows = false;
+    if (defer) {
+        StagedD2H& d = stage_out[0];
+        std::memcpy(d.dst, h_stage + d.off, d.bytes);
+        d.bytes = 0;
+    } else {
+        stage_flush();
+    }
     // rounds below r_lo are unchanged and every round up to a graph's last one has witnesses,
     // so only [r_lo, R) is scanned: last = max(that, min(previous last, r_lo - 1))
     if (r_scan > 0)
@@ -2043,8 +2130,12 @@ hipError_t Engine::divide_rounds(int64_t En, const std::vector<int32_t>& chain_l
     out.R = R;
     out.r_lo = std::min(r_lo, R);
     // the host copies keep the rows below r_lo (rows the tail copied beyond R are dropped)
-    out.bm.resize((size_t)(R + 1) * C);
-    out.wflag.resize((size_t)R * C);
+    rows_pending = defer;
+    rows_n = stage_out.size();
+    if (!defer) {
+        out.bm.resize((size_t)(R + 1) * C);
+        out.wflag.resize((size_t)R * C);
+    }
     launch_wcoin(stream, a, out.r_lo, R, C);   // (DecideFame reads the coins on this stream)
     HGX_TRY(hipGetLastError());
     float ms = 0;
@@ -2058,6 +2149,21 @@ hipError_t Engine::divide_rounds(int64_t En, const std::vector<int32_t>& chain_l
     phase_ms[1] = ms;
     step_prof_dump();   // -DHGX_STEP_PROF builds only
     return collect_kernel_times();
+}
+
+// the rows divide_rounds left in the staging (defer_rows): copied into the host tables, which get
+// their final sizes. The staging keeps them until the next stage_flush; what decide_fame_launch
+// stages meanwhile goes behind them.
+void Engine::divide_rounds_rows(RoundsHost& out) {
+    if (!rows_pending) return;
+    rows_pending = false;
+    for (size_t k = 0; k < rows_n && k < stage_out.size(); k++) {   // (not what was staged behind them)
+        StagedD2H& d = stage_out[k];
+        std::memcpy(d.dst, h_stage + d.off, d.bytes);
+        d.bytes = 0;
+    }
+    out.bm.resize((size_t)(R + 1) * C);
+    out.wflag.resize((size_t)R * C);
 }
 
 // 1 + the lowest round of an event not yet received (rounds below it cannot be a
@@ -2083,9 +2189,17 @@ int32_t Engine::recv_round_lo(const RoundsHost& rh, int& max_unrecv) const {
 
 // ---- DecideFame -----------------------------------------------------------------
 hipError_t Engine::decide_fame(int32_t r0, std::vector<int8_t>& fame_out) {
-    stage_out.clear();   // every earlier call synchronized: the staging is free
+    HGX_TRY(decide_fame_launch(r0, fame_out));
+    return fame_pending ? decide_fame_wait() : hipSuccess;
+}
+
+hipError_t Engine::decide_fame_launch(int32_t r0, std::vector<int8_t>& fame_out) {
+    fame_pending = false;
+    if (!rows_pending) {   // every earlier call synchronized: the staging is free
+        stage_out.clear();
+        stage_used = 0;
+    }   // (else divide_rounds' rows are still in it: this call's go behind them)
     pend.clear();
-    stage_used = 0;
     // rows [r0, R) are copied back below; the caller reads no row below r0, so the buffer only
     // grows (no O(R C) clear per call: the chunked schedule calls this thousands of times)
     if (fame_out.size() < (size_t)R * C) fame_out.resize((size_t)R * C, 0);
@@ -2102,6 +2216,15 @@ hipError_t Engine::decide_fame(int32_t r0, std::vector<int8_t>& fame_out) {
     HGX_TRY(stage_d2h(fame_out.data() + o, fame.p + o, fame_out.size() - o));
     HGX_TRY(stage_issue());
     HGX_TRY(hipEventRecord(ph1, stream));
+    fame_pending = true;
+    return hipSuccess;
+}
+
+hipError_t Engine::decide_fame_wait() {
+    if (!fame_pending) {   // (no round from r0: nothing was launched; the stream's earlier work is awaited all the same)
+        return hipStreamSynchronize(stream);
+    }
+    fame_pending = false;
     HGX_TRY(hipEventSynchronize(ph1));
     stage_flush();
     float ms = 0;

@@ -165,14 +165,25 @@ class Engine {
     // hgx_insert_and_run's split insert of host columns: the structure columns (creator, index,
     // parents) are staged, validated and committed now (out.graph_loaded is not final); a worker
     // thread copies the payload columns (timestamps, hash, S, transactions) of the accepted
-    // prefix on a second stream while the caller runs DivideRounds; payload_end joins it, commits
-    // the payload, rewrites the layout's timestamps and the candidates' coins, and returns the
-    // graphs' loaded counts. Not for rooted contexts (Root.Others needs the hash at validation).
+    // prefix on a second stream while the caller runs DivideRounds; payload_commit / payload_finish
+    // (below) join it, commit the payload, rewrite the layout's timestamps and the candidates' coins,
+    // and payload_loaded returns the graphs' loaded counts. Not for rooted contexts (Root.Others needs
+    // the hash at validation).
     hipError_t insert_split_begin(const int32_t* creator, const int64_t* index, const int64_t* sp, const int64_t* op,
                                   int64_t count, InsertOut& out);
     hipError_t payload_begin(const int64_t* ts, const uint8_t* hash, const uint8_t* S, const int32_t* ntx,
                              const int32_t* nil, int64_t m_ok);
-    hipError_t payload_end(int64_t E0, int64_t m_ok, bool laid_out_new, int32_t wcoin_r0, std::vector<uint64_t>& loaded);
+    // payload_end in three parts, so that no host wait stands between the rounds and DecideFame:
+    // payload_commit waits for the first columns, commits them and (positions) rewrites the layout's
+    // timestamps -- divide_rounds queues it for the compact payload ahead of k_fd_build, where the
+    // copy has landed and the coins are in place for the witnesses' coin pass; payload_finish commits
+    // what is still pending (the wide payload; a DivideRounds that did not run or failed), redoes the
+    // coins then, and queues the read-back of the graphs' loaded counts without waiting for it;
+    // payload_loaded reads them once the stream has been synchronized (DecideFame's round trip).
+    hipError_t payload_commit(bool positions, hipStream_t on = nullptr);   // (on: another stream than the context's)
+    hipError_t payload_finish(bool laid_out_new, int32_t wcoin_r0);
+    void payload_loaded(std::vector<uint64_t>& loaded) const;
+    double pay_host_ms = 0;   // host time of the three for the last payload (hgx_phase_times)
     // the compact payload's S column (copied last, straight into g_S): wait for it (the sort's
     // tie-break, a read-back, a clear) and for the caller's buffer to be read completely
     hipError_t payload_wait_S();
@@ -255,7 +266,12 @@ class Engine {
     // segments' lastAncestors main pass launched while the later pieces still cross PCIe. taken =
     // false: nothing was inserted (the path does not apply, or a check failed and the context was
     // cleared) and the caller runs insert_split_begin32 on the same columns.
+    // The copier goes on with the payload columns right behind the last piece (ts, coin, ntx into the
+    // staging columns, S straight into g_S at gid 0), so PCIe does not idle while the call finishes;
+    // taken = true leaves the payload in flight exactly as payload_begin32 would. taken = false: the
+    // copier has been joined, and whatever it wrote early is overwritten by the caller's payload_begin32.
     hipError_t insert_pipe32(const int32_t* creator, const int32_t* index, const int32_t* sp, const int32_t* op,
+                             const int64_t* ts, const uint8_t* coin, const uint8_t* S, const int32_t* ntx,
                              int64_t count, InsertOut& out, bool& taken);
     static constexpr int kPipeSegMult = 2;   // time segments of a pipelined ingest over a serial rebuild's
     int pipe_pieces = 4;                // hgx_set_ingest_pipeline: 0 = always the serial path
@@ -263,6 +279,16 @@ class Engine {
     int pipe_used = 0;                  // pieces of the last insert_and_run32 (0: serial)
     // fame of the witnesses of rounds >= r0 (the first undecided round); rows below stay 0
     hipError_t decide_fame(int32_t r0, std::vector<int8_t>& fame_out);
+    // the same in two halves: the kernel and the staged read-back queued (no wait), then the wait
+    // and the rows' copy into fame_out (the same vector, untouched in between); the caller's
+    // bookkeeping runs between the two
+    // defer_rows (set before a divide_rounds, cleared by it): the call returns with the round tables'
+    // rows still in the staging (last_round, R and r_lo are final); divide_rounds_rows copies them out,
+    // after decide_fame_launch and before anything reads RoundsHost::bm / wflag
+    bool defer_rows = false;
+    void divide_rounds_rows(RoundsHost& out);
+    hipError_t decide_fame_launch(int32_t r0, std::vector<int8_t>& fame_out);
+    hipError_t decide_fame_wait();
     // round received etc. for the events not yet received; r0 / max_unrecv from recv_round_lo
     hipError_t find_order(const std::vector<uint8_t>& elig, const std::vector<uint8_t>& famous,
                           const std::vector<uint8_t>& ur_empty, int32_t r0, int max_unrecv, OrderHost& out);
@@ -372,6 +398,11 @@ class Engine {
     hipEvent_t ev_pay_S = nullptr;
     std::atomic<int> pay_stage{0};   // 1: ts / coin / ntx (/ hash / nil) issued and ev_pay recorded
     bool pay_S_pending = false;
+    bool pay_commit_pending = false;   // the payload in flight is not committed yet (payload_commit)
+    int64_t pay_E0 = 0, pay_m = 0;     // ... its events: gids [pay_E0, pay_E0 + pay_m)
+    bool fame_pending = false;         // decide_fame_launch without its decide_fame_wait
+    bool rows_pending = false;         // divide_rounds left its rows in the staging (defer_rows)
+    size_t rows_n = 0;                 // ... the first rows_n entries of stage_out
     std::thread pay_thread;
     hipError_t pay_err = hipSuccess;
     hipError_t pay_err_a = hipSuccess;   // the compact payload's first stage (before pay_stage = 1)

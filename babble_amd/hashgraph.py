@@ -862,8 +862,8 @@ class Hashgraph:
                     pending_loaded=self.PendingLoadedEvents(graph), blocks=self.Blocks(graph))
 
     def phase_times(self):
-        out = np.zeros(23, np.float64)
-        self.L.hgx_phase_times(self.ctx, ptr(out), 23)
+        out = np.zeros(27, np.float64)
+        self.L.hgx_phase_times(self.ctx, ptr(out), 27)
         return dict(coords_ms=out[0], rounds_ms=out[1], fame_ms=out[2], order_ms=out[3],
                     la_sweeps=int(out[4]), rounds=int(out[5]), compact=int(out[6]),
                     la_rows=int(out[7]), rebuild=int(out[8]), r_lo=int(out[9]),
@@ -871,7 +871,9 @@ class Hashgraph:
                     round_p_runs=int(out[13]), round_p_fallbacks=int(out[14]), round_p_ovf=int(out[15]),
                     round_p_fail_round=int(out[16]), round_p_fail_chain=int(out[17]),
                     round_g_runs=int(out[18]), la_small=int(out[19]), la_verify=int(out[20]),
-                    sort_seg=int(out[21]), ingest_pieces=int(out[22]))
+                    sort_seg=int(out[21]), ingest_pieces=int(out[22]),
+                    host_rounds_ms=out[23], host_fame_ms=out[24], host_order_ms=out[25],
+                    payload_end_ms=out[26])
 
     def set_ingest_pipeline(self, pieces, min_events=4_000_000):
         """insert_and_run of compact columns on an empty context: the structure columns in `pieces`

@@ -656,6 +656,9 @@ int32_t hgx_p256_verify_bench(int32_t device, const uint8_t* keys65, int32_t n_k
 /* ... 1 if the last DivideRounds ran the whole graph in one workgroup, 1 if its verify sweep ran, the
  * FindOrders sorted by buckets, and the pieces of the last hgx_insert_and_run32's pipelined ingest
  * (0: the serial path) (up to 23 values) */
+/* ... then host wall clock (ms) of the last calls' host-only sections: the bookkeeping after
+ * DivideRounds' device work, after DecideFame's, before and after FindOrder's, and the time the
+ * payload commit of the last hgx_insert_and_run* took (up to 27 values) */
 int32_t hgx_phase_times(hgx_ctx* ctx, double* out, int32_t cap);
 /* dominant-kernel accounting for the roofline line of bench.py:
  * name of the kernel, summed device ms (the round steps time one hipGraph replay in four and
