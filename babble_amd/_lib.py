@@ -59,6 +59,12 @@ class hgx_wire_events(C.Structure):
                  "timestamp_ns", "hash", "sig_s", "ntx", "tx_nil")]
 
 
+class hgx_wire_bodies(C.Structure):
+    _fields_ = [(nm, C.c_void_p) for nm in
+                ("creator_id", "index", "self_parent_index", "other_parent_creator", "other_parent_index",
+                 "timestamp_ns", "sig_r", "sig_s", "ntx", "tx_off", "tx_bytes")]
+
+
 # hgx_wire_out's columns in declaration order with their numpy dtypes and row shapes
 WIRE_OUT_COLUMNS = (("gid", np.int64, ()), ("creator_id", np.int32, ()), ("index", np.int64, ()),
                     ("self_parent_index", np.int64, ()), ("other_parent_creator", np.int32, ()),
@@ -215,6 +221,7 @@ def lib():
     _sig(L, "hgx_set_shard", i32, [p, i32, i32])
     _sig(L, "hgx_reset", i32, [p, p, p, p, p])
     _sig(L, "hgx_insert_wire_events", i32, [p, p, i64, p, p])
+    _sig(L, "hgx_insert_wire_bodies", i32, [p, C.POINTER(hgx_wire_bodies), i64, p, p, p, C.POINTER(C.c_int64), E])
     _sig(L, "hgx_set_commit_callback", i32, [p, C.c_void_p, p])
     _sig(L, "hgx_get_frame", i32, [p, p, i64, p, p, p, p, p, p, p, i64, p, p])
     _sig(L, "hgx_prune_to_frame", i32, [p, p, i64, C.POINTER(C.c_int64), E])

@@ -23,6 +23,7 @@
 #include "hgx_bodies.h"
 #include "hgx_diff.h"
 #include "hgx_engine.h"
+#include "hgx_wire_plan.h"
 
 namespace {
 
@@ -494,6 +495,10 @@ static int32_t finish_insert(hgx_ctx* c, const hgx::InsertOut& out, int64_t* n_i
         case hgx::INS_BAD_KEY:   // elliptic.Unmarshal returned nil; ecdsa.Verify dereferences it
             rc = HGX_ERR_PANIC;
             msg = "runtime error: invalid memory address or nil pointer dereference";
+            break;
+        case hgx::INS_WIRE_HOLE:   // (a bug: the host plan named a resident event the window kernel did not find)
+            rc = HGX_ERR_PANIC;
+            msg = "hgx_insert_wire_bodies: a resident parent's window slot was not filled";
             break;
         default:
             rc = HGX_ERR_INVALID;
@@ -1016,6 +1021,51 @@ int32_t hgx_insert_wire_events(hgx_ctx* c, const hgx_wire_events* w, int64_t cou
         return rrc;
     }
     return HGX_OK;
+}
+
+// Core.Sync's loop over WireEvents as the wire carries them: no hash, parents as (creator id, Index)
+// (DESIGN.md §3.14). The host plan (hgx_wire_plan.h) decides ReadWireInfo's errors and the in-batch
+// parents from the per-chain mirrors; the gids of the resident parents are found on the device, then the
+// prefix before the first resolution error takes the body path (Event.Hash, Event.Verify, InsertEvent),
+// whose first failure comes first. The host mirror of the event columns is neither built nor read.
+int32_t hgx_insert_wire_bodies(hgx_ctx* c, const hgx_wire_bodies* w, int64_t count, uint8_t* out_id32,
+                               int64_t* out_self_parent, int64_t* out_other_parent, int64_t* n_inserted,
+                               hgx_error* err) {
+    const std::string who = "hgx_insert_wire_bodies: ";
+    auto bad = [&](const std::string& why) {
+        set_err(err, HGX_ERR_INVALID, who + why);
+        return (int32_t)HGX_ERR_INVALID;
+    };
+    if (n_inserted) *n_inserted = 0;
+    if (!w || count < 0) return bad("bad arguments");
+    if (count > 0 && !w->other_parent_creator) return bad("null column");
+    const hgx::BodiesIn cols{w->creator_id, w->index, w->self_parent_index, w->other_parent_index, w->timestamp_ns,
+                             w->sig_r, w->sig_s, w->ntx, w->tx_off, w->tx_bytes};
+    std::vector<int64_t> txi;
+    if (const char* why = hgx::bodies_check(cols, count, txi)) return bad(why);
+    if (!c) return bad("bad arguments");
+    if (c->G > 1) return bad("not available on a batched context");
+    if (c->grp) return bad("not available on a chain-sharded context");
+    if (c->shard_world > 1) return bad("not available on a row-sharded context");
+    if (c->rooted && !c->root_ids_known) return bad("not after hgx_reset without root ids (hgx_set_root_ids)");
+    if (!c->eng.keys_set) return bad("participant keys not set");
+    if (!c->eng.ids_known) return bad("ids not known (the context holds events inserted without their ids)");
+    DeviceGuard dg(c);
+    hgx::WirePlan plan;
+    hgx::wire_plan(hgx::WireIn{w->creator_id, w->index, w->self_parent_index, w->other_parent_creator,
+                               w->other_parent_index},
+                   count, c->last_index.data(), c->chain_len.data(), c->n, c->E, plan);
+    // the prefix with the plan's descriptors as its parent columns
+    const hgx::BodiesIn ev{w->creator_id, w->index, plan.sp.data(), plan.op.data(), w->timestamp_ns,
+                           w->sig_r, w->sig_s, w->ntx, w->tx_off, w->tx_bytes};
+    const hgx::Engine::WireWindows win{plan.lo.data(), plan.woff.data(), plan.slots, plan.n_resident};
+    hgx::InsertOut out;
+    const hipError_t e = c->eng.insert_wire_bodies(ev, txi, plan.m, win, out_id32, out_self_parent, out_other_parent, out);
+    if (e != hipSuccess) return dev_err(err, e, "hgx_insert_wire_bodies");
+    const int32_t rc = finish_insert(c, out, n_inserted, err);
+    if (rc != HGX_OK || plan.code == HGX_OK) return rc;
+    set_err(err, plan.code, plan.msg);
+    return plan.code;
 }
 
 static int32_t insert_events_device_one(hgx_ctx* c, const hgx_events* ev, int64_t count, int64_t* n_inserted,

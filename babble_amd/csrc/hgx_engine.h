@@ -145,6 +145,18 @@ class Engine {
     // other-parents, 32 bytes per event (read on a context with root ids only).
     hipError_t insert_bodies(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count, const uint8_t* op_id32,
                              uint8_t* out_id32, InsertOut& out);
+    // The same for a SyncResponse's wire events (hgx_wire.hip): ev.sp / ev.op hold the
+    // host plan's parent descriptors (hgx_wire_plan.h), lo / woff / slots its windows. The window is
+    // filled once against the resident events (not launched when n_resident == 0), every chunk's
+    // descriptors become gids on the device before the encoder reads them, then insert_bodies' chunks
+    // unchanged. out_sp / out_op (host, may be null) get the accepted prefix's parent gids.
+    struct WireWindows {
+        const int32_t *lo, *woff;   // [n]
+        int64_t slots, n_resident;
+    };
+    hipError_t insert_wire_bodies(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count,
+                                  const WireWindows& w, uint8_t* out_id32, int64_t* out_sp, int64_t* out_op,
+                                  InsertOut& out);
     EvScratch* ev_scratch = nullptr;
     // The roots' ids on the device: Root.X / Root.Y per chain and the Root.Others
     // pairs sorted by event id, the text of the parents that are in no id column. has_x / has_y: [C];
@@ -375,6 +387,14 @@ class Engine {
     hipError_t ensure_round_cap(int32_t need);
     hipError_t insert_impl(const InsertIn& in, int64_t count, InsertOut& out, const unsigned long long* fail_sig,
                            int commit_mode = kCommitAll);
+    // insert_bodies' chunk loop; wire: the parent columns carry window descriptors (insert_wire_bodies)
+    struct WireRun {
+        const int32_t* win;   // the filled window (device)
+        int64_t slots;
+        int64_t *out_sp, *out_op;
+    };
+    hipError_t insert_bodies_run(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count,
+                                 const uint8_t* op_id32, uint8_t* out_id32, InsertOut& out, const WireRun* wire);
     hipStream_t stream2 = nullptr;   // payload copies of insert_split (created on first use)
     // the pipelined ingest: stream_p and stream_o take the pieces' k_la_wave launches in turn
     void layout_slots(int64_t En, const std::vector<int32_t>& chain_len, std::vector<int32_t>& off) const;

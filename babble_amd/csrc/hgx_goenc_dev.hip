@@ -457,7 +457,15 @@ struct EvScratch {
     size_t h_cap = 0;
     LevelPlan plan;
     std::vector<int32_t> level;
-    ~EvScratch() { if (h) (void)hipHostFree(h); }
+    // hgx_insert_wire_bodies: lo[n] | woff[n], then the window (4 bytes per slot); the
+    // table goes up from a page-locked copy
+    DevMem wire;
+    int32_t* h_wtab = nullptr;
+    size_t h_wtab_cap = 0;
+    ~EvScratch() {
+        if (h) (void)hipHostFree(h);
+        if (h_wtab) (void)hipHostFree(h_wtab);
+    }
 
     // device views of the staged chunk
     EvCols cols{};
@@ -570,6 +578,43 @@ void free_ev_scratch(EvScratch* p) { delete p; }
 // with each chunk and the Others value check runs before the insert.
 hipError_t Engine::insert_bodies(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count, const uint8_t* op_id32,
                                  uint8_t* out_id32, InsertOut& out) {
+    return insert_bodies_run(ev, txi, count, op_id32, out_id32, out, nullptr);
+}
+
+// The wire route (hgx_insert_wire_bodies): the window of the resident parents is filled once, against
+// the events resident before the call; a later chunk's parents in an earlier chunk are final gids.
+hipError_t Engine::insert_wire_bodies(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count,
+                                      const WireWindows& w, uint8_t* out_id32, int64_t* out_sp, int64_t* out_op,
+                                      InsertOut& out) {
+    if (G != 1 || n > 1024 || w.slots < 0 || w.slots > E) return hipErrorInvalidValue;
+    if (!ev_scratch) ev_scratch = new EvScratch();
+    EvScratch& sc = *ev_scratch;
+    WireRun run{nullptr, 0, out_sp, out_op};
+    if (count > 0 && w.n_resident > 0) {
+        const size_t tab = up256(8 * (size_t)n);
+        HGX_TRY(sc.wire.need(tab + 4 * (size_t)w.slots));
+        if (sc.h_wtab_cap < tab) {
+            if (sc.h_wtab) (void)hipHostFree(sc.h_wtab);
+            sc.h_wtab = nullptr;
+            sc.h_wtab_cap = 0;
+            HGX_TRY(hipHostMalloc((void**)&sc.h_wtab, tab, hipHostMallocDefault));
+            sc.h_wtab_cap = tab;
+        }
+        std::memcpy(sc.h_wtab, w.lo, 4 * (size_t)n);
+        std::memcpy(sc.h_wtab + n, w.woff, 4 * (size_t)n);
+        int32_t* win = (int32_t*)(sc.wire.p + tab);
+        HGX_TRY(hipMemcpyAsync(sc.wire.p, sc.h_wtab, 8 * (size_t)n, hipMemcpyHostToDevice, stream));
+        HGX_TRY(hipMemsetAsync(win, 0xFF, 4 * (size_t)w.slots, stream));   // -1: a slot nobody filled
+        launch_wire_window(stream, WireWinArgs{E, n, g_creator.p, g_index.p, (const int32_t*)sc.wire.p, win, w.slots});
+        HGX_TRY(hipGetLastError());
+        run.win = win;
+        run.slots = w.slots;
+    }
+    return insert_bodies_run(ev, txi, count, nullptr, out_id32, out, &run);
+}
+
+hipError_t Engine::insert_bodies_run(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count,
+                                     const uint8_t* op_id32, uint8_t* out_id32, InsertOut& out, const WireRun* wire) {
     if (!ev_scratch) ev_scratch = new EvScratch();
     EvScratch& sc = *ev_scratch;
     int64_t done = 0;
@@ -587,6 +632,9 @@ hipError_t Engine::insert_bodies(const BodiesIn& ev, const std::vector<int64_t>&
         const int64_t hi = bodies_chunk_end(ev, txi, done, count, &bound);
         const int64_t m = hi - done;
         HGX_TRY(sc.stage(ev, txi, done, hi, pk_keys.p, nullptr, C, nullptr, nullptr, true, E, n, stream, rt.has_x, op_id32));
+        if (wire && wire->win)   // window descriptors -> gids, before the encoder reads the parent columns
+            launch_wire_resolve(stream, m, const_cast<int64_t*>(sc.cols.sp), const_cast<int64_t*>(sc.cols.op), wire->win,
+                                wire->slots, ins_fail.p);
         HGX_TRY(sc.size_and_scan(m, 16, stream));
         HGX_TRY(sc.write(m, (size_t)bound, true, stream));
         const int bs = std::min(1024, std::max(64, (sc.plan.max_width + 63) & ~63));
@@ -605,8 +653,22 @@ hipError_t Engine::insert_bodies(const BodiesIn& ev, const std::vector<int64_t>&
         in.ts = sc.cols.ts; in.hash = sc.d_ids; in.S = sc.cols.s; in.ntx = sc.cols.ntx; in.nil = nullptr;
         InsertOut co;
         HGX_TRY(insert_verified(in, sc.d_dig, sc.cols.r, m, co));
-        if (out_id32 && co.accepted > 0) {
-            HGX_TRY(hipMemcpyAsync(out_id32 + 32 * done, sc.d_ids, 32 * (size_t)co.accepted, hipMemcpyDeviceToHost, stream));
+        if (wire && wire->win && co.code) {
+            // a window slot nobody filled made this event fail its checks: that bug is the finding
+            int64_t par[2] = {0, 0};
+            HGX_TRY(hipMemcpyAsync(&par[0], sc.cols.sp + co.accepted, 8, hipMemcpyDeviceToHost, stream));
+            HGX_TRY(hipMemcpyAsync(&par[1], sc.cols.op + co.accepted, 8, hipMemcpyDeviceToHost, stream));
+            HGX_TRY(hipStreamSynchronize(stream));
+            if (par[0] == kWireHoleParent || par[1] == kWireHoleParent) co.code = INS_WIRE_HOLE;
+        }
+        const bool want_par = wire && (wire->out_sp || wire->out_op);
+        if ((out_id32 || want_par) && co.accepted > 0) {
+            const size_t acc = (size_t)co.accepted;
+            if (out_id32) HGX_TRY(hipMemcpyAsync(out_id32 + 32 * done, sc.d_ids, 32 * acc, hipMemcpyDeviceToHost, stream));
+            if (wire && wire->out_sp)
+                HGX_TRY(hipMemcpyAsync(wire->out_sp + done, sc.cols.sp, 8 * acc, hipMemcpyDeviceToHost, stream));
+            if (wire && wire->out_op)
+                HGX_TRY(hipMemcpyAsync(wire->out_op + done, sc.cols.op, 8 * acc, hipMemcpyDeviceToHost, stream));
             HGX_TRY(hipStreamSynchronize(stream));
         }
         done += co.accepted;

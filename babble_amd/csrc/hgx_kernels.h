@@ -101,8 +101,10 @@ constexpr int64_t kRootY = -3, kRootOther = -4;
 enum InsertCode {
     INS_OK = 0, INS_KEY_NOT_FOUND = 1, INS_SELF_PARENT = 2, INS_OTHER_PARENT = 3, INS_CAPACITY = 4,
     INS_PASSED_INDEX = 5, INS_SKIPPED_INDEX = 6, INS_INDEX_RANGE = 7,
-    INS_BAD_SIG = 8, INS_BAD_KEY = 9   // Event.Verify: invalid signature / creator key not a P-256 point
+    INS_BAD_SIG = 8, INS_BAD_KEY = 9,  // Event.Verify: invalid signature / creator key not a P-256 point
+    INS_WIRE_HOLE = 10                 // hgx_insert_wire_bodies: a parent's window slot was never filled (a bug)
 };
+constexpr int64_t kWireHoleParent = -2;   // HGX_UNKNOWN_PARENT (include/hgx.h)
 
 // arguments of the round step (hgx_rounds.hip)
 struct RoundArgs {
@@ -409,5 +411,24 @@ struct DiffArgs {
 };
 constexpr int kDiffChunk = 2048;   // gids per workgroup (= k_scan_top's partials)
 void launch_diff(hipStream_t s, const DiffArgs& a);
+
+// hgx_insert_wire_bodies (hgx_wire.hip): the gids of the resident events a batch names
+// as parents. tab = lo[n] | woff[n] (hgx_wire_plan.h): the event of creator c with Index >= lo[c] has its
+// gid at win[woff[c] + Index - lo[c]]. win holds `slots` entries, preset to -1 by the caller.
+struct WireWinArgs {
+    int64_t E;                 // resident events
+    int n;
+    const int32_t *g_creator, *g_index;
+    const int32_t* tab;
+    int32_t* win;
+    int64_t slots;
+};
+constexpr int kWireChunk = 2048;   // gids per workgroup
+void launch_wire_window(hipStream_t s, const WireWinArgs& a);
+// The staged parent columns of m chunk events: a window descriptor (<= -2, slot -2 - d) becomes
+// win[slot]. A slot nobody filled becomes HGX_UNKNOWN_PARENT (which no wire event can carry) and
+// files (k << 8 | INS_WIRE_HOLE) in *fail, the insert's first-failure word.
+void launch_wire_resolve(hipStream_t s, int64_t m, int64_t* sp, int64_t* op, const int32_t* win, int64_t slots,
+                         unsigned long long* fail);
 
 }  // namespace hgx

@@ -129,6 +129,32 @@ def _event_bodies_of(cols: dict, lo: int, hi: int):
                                                           "tx_off", "tx_bytes")])
 
 
+_WIRE_BODY_FIELDS = ("creator_id", "index", "self_parent_index", "other_parent_creator", "other_parent_index",
+                     "timestamp_ns", "sig_r", "sig_s", "ntx", "tx_off", "tx_bytes")
+
+
+def wire_body_columns(rows: dict, r, txs) -> dict:
+    """hgx_wire_bodies columns (include/hgx.h) from DiffWire rows (creator_id, index, self_parent_index,
+    other_parent_creator, other_parent_index, timestamp_ns, sig_s: any mapping with these names), the
+    signatures' R (32 bytes big-endian each) and txs[k] = Body.Transactions of row k (None for nil,
+    else a list of byte strings): a SyncResponse as the peer decodes it."""
+    b = body_columns(rows["creator_id"], rows["index"], rows["self_parent_index"], rows["other_parent_index"],
+                     rows["timestamp_ns"], r, rows["sig_s"], txs)
+    return dict(creator_id=b["creator"], index=b["index"], self_parent_index=b["sp"],
+                other_parent_creator=np.ascontiguousarray(rows["other_parent_creator"], np.int32),
+                other_parent_index=b["op"], timestamp_ns=b["ts"], sig_r=b["r"], sig_s=b["s"], ntx=b["ntx"],
+                tx_off=b["tx_off"], tx_bytes=b["tx_bytes"])
+
+
+def _wire_bodies_of(cols: dict, lo: int, hi: int):
+    """The hgx_wire_bodies of events [lo, hi) (tx_off starts at the slice's first transaction)."""
+    a = {k: np.ascontiguousarray(cols[k][lo:hi]) for k in _WIRE_BODY_FIELDS[:9]}
+    first = int(np.maximum(cols["ntx"][:lo], 0).sum())
+    a["tx_off"] = np.ascontiguousarray(cols["tx_off"][first:])
+    a["tx_bytes"] = cols["tx_bytes"]
+    return a, _lib.hgx_wire_bodies(*[ptr(a[k]) for k in _WIRE_BODY_FIELDS])
+
+
 def event_json_batch(cols: dict, keys65, sp_id32, op_id32, device: int = 0, out_cap: Optional[int] = None):
     """Event.Marshal bytes of body_columns() events whose parents' ids the caller supplies
     (hgx_event_json_batch). Returns (data, offsets): event k's text is data[offsets[k]:offsets[k+1]].
@@ -316,6 +342,28 @@ class Hashgraph:
             e.inserted = n_ins.value
             raise e
         return n_ins.value
+
+    def insert_wire_bodies(self, cols: dict, lo: int = 0, hi: Optional[int] = None):
+        """Core.Sync's loop over WireEvents from their wire fields alone (hgx_insert_wire_bodies): events
+        [lo, hi) of wire_body_columns(); parents resolved, ids hashed and signatures verified on the device.
+        Returns (ids [(hi - lo), 32], self_parent gids, other_parent gids; -1 for ""). On the first error
+        raises HgxError with .inserted = events inserted before it and .ids / .self_parent / .other_parent
+        = theirs."""
+        hi = len(cols["creator_id"]) if hi is None else hi
+        a, ev = _wire_bodies_of(cols, lo, hi)
+        ids = np.zeros((hi - lo, 32), np.uint8)
+        sp = np.full(hi - lo, -1, np.int64)
+        op = np.full(hi - lo, -1, np.int64)
+        err = hgx_error()
+        n_ins = C.c_int64(0)
+        rc = self.L.hgx_insert_wire_bodies(self.ctx, C.byref(ev), hi - lo, ptr(ids), ptr(sp), ptr(op), C.byref(n_ins),
+                                           C.byref(err))
+        if rc:
+            e = HgxError(int(err.code or rc), err.msg.decode(errors="replace"))
+            e.inserted = n_ins.value
+            e.ids, e.self_parent, e.other_parent = ids[:n_ins.value], sp[:n_ins.value], op[:n_ins.value]
+            raise e
+        return ids, sp, op
 
     def insert_device(self, dt: "DeviceTrace", lo: int = 0, hi: Optional[int] = None) -> int:
         """Bulk InsertEvent of a trace already resident in HBM (hgx_insert_events_device)."""

@@ -37,7 +37,8 @@ extern "C" {
 #endif
 
 #define HGX_ABI_VERSION 6   /* (still 6 with hgx_insert_event_bodies(_ext), hgx_set_root_ids, hgx_event_json_batch and hgx_batch_levels,
-                                 with hgx_prune_to_frame, hgx_get_root_ids and hgx_get_root_others, and with hgx_diff_wire:
+                                 with hgx_prune_to_frame, hgx_get_root_ids and hgx_get_root_others, with hgx_diff_wire, and
+                                 with hgx_insert_wire_bodies:
                                  purely additive, no existing entry or structure changed)
                               6: hgx_host_alloc / hgx_host_free (page-locked caller buffers);
                               5: hgx_events_packed (hgx_insert_events_packed, hgx_insert_and_run_packed,
@@ -306,6 +307,52 @@ typedef struct {
  * events) then InsertEvent(ev, false); stops at the first error with Go's string (the
  * ReadWireInfo errors "<index>, Too Late" / "<index>, Not Found" included). */
 int32_t hgx_insert_wire_events(hgx_ctx* ctx, const hgx_wire_events* ev, int64_t count, int64_t* n_inserted,
+                               hgx_error* err);
+/* WireEvents exactly as a peer sends them (event.go:252-267): no hash, parents as (creator id, Index).
+ * These are hgx_diff_wire's columns plus R and the transactions. */
+typedef struct {
+    const int32_t* creator_id;            /* WireBody.CreatorID, 0..n-1 */
+    const int64_t* index;                 /* WireBody.Index */
+    const int64_t* self_parent_index;     /* < 0: no self-parent */
+    const int32_t* other_parent_creator;  /* read only where other_parent_index >= 0 */
+    const int64_t* other_parent_index;    /* < 0: "" */
+    const int64_t* timestamp_ns;
+    const uint8_t* sig_r;                 /* 32 B big-endian each */
+    const uint8_t* sig_s;
+    const int32_t* ntx;                   /* -1 for nil, as hgx_event_bodies */
+    const int64_t* tx_off;                /* as hgx_event_bodies */
+    const uint8_t* tx_bytes;
+} hgx_wire_bodies;
+/* Core.Sync's insert loop (node/core.go:199-211) from the wire fields alone: per
+ * event ReadWireInfo (hashgraph.go:569-614), then InsertEvent(ev, false) with Event.Hash and
+ * Event.Verify on the device as hgx_insert_event_bodies does them; stops at the first error with Go's
+ * string. A parent (creator, Index) resolves as Store.ParticipantEvent does over the participant's
+ * resident events plus the batch's earlier events, positionally (RollingIndex.GetItem): "<rune>, Too
+ * Late" (HGX_ERR_TOO_LATE) below the chain's oldest Index, "<rune>, Not Found" (HGX_ERR_KEY_NOT_FOUND)
+ * above the last event inserted so far -- a parent at a later batch position included --, and
+ * HGX_ERR_PANIC "runtime error: slice bounds out of range [2:0]" / "runtime error: invalid memory
+ * address or nil pointer dereference" for a creator id / an other-parent creator id outside 0..n-1.
+ * A resolution error at position m cuts the batch: events [0, m) take the body path, whose failure, if
+ * any, is the call's; otherwise the call returns the resolution error with *n_inserted = m. For the
+ * prefix everything equals hgx_insert_event_bodies_ext on the same events with the parents as gids:
+ * ids, error strings and their order, hgx_get_event_id, the context's state.
+ * out_id32 (32 bytes per event), out_self_parent and out_other_parent (the resolved parent gids, -1 for
+ * "") receive the accepted prefix; each may be NULL.
+ * On a context with known root ids a self-parent index < 0 prints the creator's Root.X id (§3.12); an
+ * index >= 0 resolves like any other. A wire event cannot name HGX_ROOT_Y / HGX_ROOT_OTHER.
+ * Nothing proportional to the resident events crosses to the host, and the host mirror of the event
+ * columns is neither built nor read: the plan uses the per-chain tables every insert keeps, the gids
+ * of the resident parents are looked up on the device.
+ * HGX_ERR_INVALID "hgx_insert_wire_bodies: <reason>", nothing changed: bad columns (as
+ * hgx_insert_event_bodies, checked first), ctx NULL, a batch (G > 1), chain-sharded or row-sharded
+ * context, roots whose ids are not known, keys not set, ids not known.
+ * Scratch, on top of hgx_insert_event_bodies': the window of resident parents, 4 bytes per slot, one
+ * slot per Index from the smallest one the batch names of a chain to that chain's head -- a few KB for a
+ * sync between peers that gossip regularly, at worst 4 bytes per resident event (a batch naming every
+ * chain's oldest event) --, plus 8 bytes per participant. The plan's parent descriptors travel in the
+ * chunk's two parent columns (16 bytes per event), which the body path stages anyway. */
+int32_t hgx_insert_wire_bodies(hgx_ctx* ctx, const hgx_wire_bodies* ev, int64_t count, uint8_t* out_id32,
+                               int64_t* out_self_parent, int64_t* out_other_parent, int64_t* n_inserted,
                                hgx_error* err);
 int32_t hgx_divide_rounds(hgx_ctx* ctx, hgx_error* err);
 int32_t hgx_decide_fame(hgx_ctx* ctx, hgx_error* err);
