@@ -2818,8 +2818,8 @@ int32_t hgx_witness(hgx_ctx* c, int64_t x) {
 // ---- instrumentation / knobs ----------------------------------------------------------
 int32_t hgx_phase_times(hgx_ctx* c, double* out, int32_t cap) {
     if (!c || !out) return 0;
-    const int32_t m = std::min<int32_t>(cap, 27);
-    double v[27] = {c->eng.phase_ms[0], c->eng.phase_ms[1], c->eng.phase_ms[2], c->eng.phase_ms[3],
+    const int32_t m = std::min<int32_t>(cap, 28);
+    double v[28] = {c->eng.phase_ms[0], c->eng.phase_ms[1], c->eng.phase_ms[2], c->eng.phase_ms[3],
                     (double)c->eng.la_sweeps, (double)c->eng.R, (double)c->eng.compact,
                     (double)c->eng.la_rows, c->eng.last_rebuild ? 1.0 : 0.0, (double)c->rh.r_lo,
                     c->eng.la_wave_used ? 1.0 : 0.0, (double)c->eng.la_wave_fallbacks,
@@ -2828,7 +2828,7 @@ int32_t hgx_phase_times(hgx_ctx* c, double* out, int32_t cap) {
                     (double)c->eng.round_p_fail_round, (double)c->eng.round_p_fail_chain,
                     (double)c->eng.round_g_runs, c->eng.la_small_used ? 1.0 : 0.0,
                     c->eng.la_verified ? 1.0 : 0.0, (double)c->eng.sort_seg_runs, (double)c->eng.pipe_used,
-                    c->host_ms[0], c->host_ms[1], c->host_ms[2], c->host_ms[3]};
+                    c->host_ms[0], c->host_ms[1], c->host_ms[2], c->host_ms[3], (double)c->eng.cts_row_runs};
     for (int32_t i = 0; i < m; i++) out[i] = v[i];
     return m;
 }
@@ -3089,8 +3089,8 @@ hgx_ctx* hgx_create_sharded(int32_t n_participants, int64_t capacity_events, int
 }
 
 int32_t hgx_set_cts_kernel(hgx_ctx* c, int32_t mode) {
-    if (!c || mode < 0 || mode > 2) return HGX_ERR_INVALID;
-    each_shard(c, [&](hgx_ctx* x) { x->eng.cts_kernel = mode == 0 ? 1 : mode; });
+    if (!c || mode < 0 || mode > 4) return HGX_ERR_INVALID;
+    each_shard(c, [&](hgx_ctx* x) { x->eng.cts_kernel = mode; });
     return HGX_OK;
 }
 

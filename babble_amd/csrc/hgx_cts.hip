@@ -327,4 +327,245 @@ bool launch_cts_pipe(hipStream_t s, const DevArrays& a, int c_lo, int c_cnt, int
                      : launch_cts_pipe_t<int32_t>(s, a, c_lo, c_cnt, C, n, P, max_cnt);
 }
 
+// ---------------------------------------------------------------------------------
+// Round 9: lane = event, instruction = witness chain (k_cts_small's mapping for 32 < n <= 256).
+// A block owns TP = 64 consecutive positions of one chain. In phase 1 a wave's 64 lanes are the
+// tile's events and every wave walks NPAD / NW witness chains: FDT[c][p0 .. p0 + TP) is one
+// coalesced load whose lines are used whole (k_cts_tile's instruction touches 8 columns for
+// 16 bytes each), and since firstDescendants are monotone along a chain the TP timestamp
+// gathers of a chain fall into a few lines. The per-chain terms are wave-uniform (read from a
+// lane). The gathered values go to LDS as k_cts_tile's 32-bit offsets, vals[c][e]; phase 2 is
+// k_cts_tile's: one wave per event, radix select of element floor(m/2).
+// Membership (WLAT[(rr, tc)][c] >= Index) needs the row of the event's round received; rr is
+// non-decreasing along a chain and TP positions span a few rounds, so the block stages the K
+// rows from its smallest rr in LDS (loads issued beside the gathers) and an event beyond them
+// reads its row from global memory.
+// Measured at c3: 6.46 ms against k_cts_tile's 7.0; 3.3 ms without the selects.
+constexpr int kRowKMax = 8;   // staged WLAT rows at most
+constexpr int kRowTP = 64;    // positions per block = lanes of a wave (32 with two chains per instruction: c3 7.13 - 7.24 ms, removed)
+constexpr int kRowD = 16;     // chain instructions in flight per wave (4: 6.55, 8: 6.63 - 6.66, 32: 6.57 ms)
+// waves per block: vals lets two blocks share a CU whatever their size, and the selects of phase 2
+// need waves to hide behind (c3: 4 waves 10.3 - 10.5 ms, 8: 6.9, 16: 9.0, before the per-chain
+// terms moved from scalar loads to a lane: 8 waves 6.9 -> 6.46)
+constexpr int row_waves(int npad) { return npad >= 128 ? 8 : 4; }
+
+template <int NPAD, typename CT, int TP, int DREQ, int NW>
+__global__ void __launch_bounds__(64 * NW) k_cts_row(const int32_t* __restrict__ fu, const int32_t* __restrict__ rcnt,
+                                                 const int32_t* __restrict__ p_rr, const int32_t* __restrict__ c_off,
+                                                 const int32_t* __restrict__ c_base, const int32_t* __restrict__ WLAT,
+                                                 const CT* __restrict__ FDT, const int64_t* __restrict__ p_ts,
+                                                 int64_t* __restrict__ p_cts, int C, int n, int64_t Pcap, int c_lo,
+                                                 int c_cnt, int R, int K) {
+    static_assert(TP == 64, "k_cts_row: a wave's lanes are the block's events");
+    constexpr int LD = TP + 1;            // row stride of vals: conflict-free for both phases
+    constexpr int CPL = NPAD / 64;
+    constexpr int CW = NPAD / NW;         // chains per wave
+    constexpr int NI = CW;                // chain instructions per wave: instruction k takes chain wc0 + k
+    constexpr int D = DREQ < NI ? DREQ : NI;
+    constexpr int NB = NI / D;
+    constexpr int MB = NPAD / 8;          // membership bytes per event
+    static_assert(NI % D == 0 && NI % 8 == 0 && NI <= 64, "k_cts_row: batches and membership bytes");
+    constexpr int RG = 64 * NW / NPAD;    // staged rows loaded at once (thread t: word t % NPAD of row t / NPAD)
+    constexpr int KL = kRowKMax / RG;     // staging loads per thread
+    static_assert(RG >= 1 && kRowKMax % RG == 0, "k_cts_row: staging loads");
+    // [NPAD][LD] offsets + 2^31 | wl[K][n + 1], reused by phase 2 as the waves' histograms [NW][256]
+    extern __shared__ __attribute__((aligned(16))) uint32_t vals[];
+    int32_t* wl = (int32_t*)(vals + NPAD * LD);
+    __shared__ uint8_t mem[TP][MB];
+    __shared__ int32_t e_row[TP];
+    __shared__ int64_t e_ts[TP];
+    __shared__ int32_t e_ovf[TP];
+    __shared__ uint32_t s_min[NW];
+    // time-major blocks (b = tile * c_cnt + chain): the blocks in flight gather timestamps of the
+    // same period on every chain and share those lines in L2. Tiles are cut at multiples of TP
+    // from the 32-position boundary below the chain's first new event (chain slots and the
+    // column stride are multiples of 32 positions, so an FD load starts 64-byte aligned); a
+    // chain's first tile may be short.
+    const int cl = (int)(blockIdx.x % (unsigned)c_cnt), tt = (int)(blockIdx.x / (unsigned)c_cnt);
+    const int tc = c_lo + cl;
+    const int f0 = fu[tc], co = c_off[tc];
+    const int64_t q0 = (int64_t)co + f0, pend = q0 + rcnt[tc];
+    const int64_t ps = (int64_t)co + (f0 & ~31) + (int64_t)tt * TP;
+    // (block-uniform) no event in this tile. A chain that receives nothing has ps <= q0 = pend when its
+    // fu is off a 32-position boundary: q0 may then be past the chain's last event, where
+    // firstDescendants are not defined, so nothing may be loaded from it.
+    if ((ps > q0 ? ps : q0) >= pend) return;
+    const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int e = lane;
+    const int64_t p = ps + e;
+    const bool ev = p >= q0 && p < pend;
+    const int64_t pl = ev ? p : (ps > q0 ? ps : q0);   // a valid position for the loads of a missing event
+    const int i = p_rr[pl];
+    const int64_t base = p_ts[pl];
+    const int g = tc / n, gb = g * n;
+    const int j = c_base[tc] + (int)(pl - co);
+    const bool evi = ev && i >= 0;
+    const int wc0 = wave * CW;
+    uint32_t* whist = vals + NPAD * LD + 256 * wave;
+    // chain of instruction k in this lane, clamped to a chain of the graph (a chain >= n loads
+    // valid addresses and is never a member)
+    auto chain = [&](int k) { const int c = wc0 + k; return c < n ? c : 0; };
+    auto load_fd = [&](int b, CT (&fd)[D]) {
+#pragma unroll
+        for (int u = 0; u < D; u++) fd[u] = FDT[(size_t)chain(b * D + u) * Pcap + pl];
+    };
+    CT fd[2][D];
+    load_fd(0, fd[0]);
+    // c_off - c_base of the wave's chains, one per lane: an instruction's term is read from its
+    // lane into an SGPR (a scalar load per chain put its latency in front of every gather)
+    const int kc = wc0 + lane < n && lane < CW ? wc0 + lane : 0;
+    const int32_t kdv = c_off[gb + kc] - c_base[gb + kc];
+    // the block's smallest round received (level 1 only: the FD loads above stay in flight)
+    const uint32_t wmin = wave_reduce_min_u32(evi ? (uint32_t)i : 0x7fffffffu);
+    if (lane == 0) s_min[wave] = wmin;
+    if (threadIdx.x < TP) {
+        e_row[e] = evi ? i : -1;
+        e_ts[e] = base;
+        e_ovf[e] = 0;
+    }
+    cp_lds_barrier();
+    uint32_t bmin = s_min[0];
+#pragma unroll
+    for (int w = 1; w < NW; w++) bmin = min(bmin, s_min[w]);
+    const int imin = bmin == 0x7fffffffu ? 0 : (int)bmin;
+    // rows imin .. imin + K - 1 of (round, tc), clamped to the rounds that exist: level 2, beside
+    // the gathers. Every load is issued (a row past K or a word past n repeats a valid one and
+    // is dropped).
+    int32_t st[KL];
+    const int sw = (int)threadIdx.x % NPAD, srow = (int)threadIdx.x / NPAD;
+#pragma unroll
+    for (int q = 0; q < KL; q++)
+        st[q] = WLAT[((size_t)min(imin + min(q * RG + srow, K - 1), R - 1) * C + tc) * n + min(sw, n - 1)];
+    // The chains' pipeline, in program order (the memory counter retires in order, so a wait
+    // for a batch leaves the batches issued after it in flight):
+    //    F0 F1 G0 | F2 G1 use0 | F3 G2 use1 | ...
+    // F = a batch's D FD loads, G = its timestamp gathers, use = offsets to LDS. The compiler
+    // barriers keep that order: without them the address arithmetic of a later batch's FD values
+    // was scheduled right behind each load and every load waited for on its own.
+    int64_t x[2][D];
+    auto gather = [&](int b, const CT (&f)[D], int64_t (&xo)[D]) {
+#pragma unroll
+        for (int u = 0; u < D; u++) {
+            const int k = b * D + u;
+            const int32_t kd = __builtin_amdgcn_readlane(kdv, k);   // the instruction's chain: wave-uniform
+            const int32_t fv = Coord<CT>::fd(f[u]);
+            xo[u] = p_ts[fv != kMaxI32 ? kd + fv : 0];
+        }
+    };
+    uint64_t ovm = 0;   // bit k: the offset of instruction k's chain does not fit 32 bits
+    if (NB > 1) load_fd(1, fd[1]);
+    cp_order();
+    gather(0, fd[0], x[0]);
+    cp_order();
+#pragma unroll
+    for (int b = 0; b < NB; b++) {
+        if (b + 2 < NB) load_fd(b + 2, fd[b & 1]);
+        cp_order();
+        if (b + 1 < NB) gather(b + 1, fd[(b + 1) & 1], x[(b + 1) & 1]);
+        cp_order();
+#pragma unroll
+        for (int u = 0; u < D; u++) {
+            const int k = b * D + u;
+            const int64_t dlt = x[b & 1][u] - base;
+            ovm |= (uint64_t)(dlt < INT32_MIN || dlt > INT32_MAX) << k;
+            vals[(wc0 + k) * LD + e] = (uint32_t)(int32_t)dlt ^ 0x80000000u;
+        }
+        cp_order();
+    }
+    const int WS = n + 1;   // row stride of the staged rows (lanes of different rounds: different banks)
+#pragma unroll
+    for (int q = 0; q < KL; q++)
+        if (q * RG + srow < K && sw < n) wl[(q * RG + srow) * WS + sw] = st[q];
+    __syncthreads();
+    {
+        uint64_t okm = 0;   // bit k: the chain of instruction k is a member
+        if (!evi || i - imin < K) {
+            const int32_t* row = wl + (evi ? i - imin : 0) * WS;
+#pragma unroll
+            for (int k = 0; k < NI; k++) okm |= (uint64_t)(row[chain(k)] >= j) << k;
+        } else {   // a tile spanning more than K rounds
+            const int32_t* __restrict__ row = WLAT + ((size_t)i * C + tc) * n;
+#pragma unroll
+            for (int k = 0; k < NI; k++) okm |= (uint64_t)(row[chain(k)] >= j) << k;
+        }
+        // (chains >= n: the last chains of the last wave in use, k >= n - wc0)
+        const int live = n - wc0;
+        if (live < NI) okm &= live > 0 ? ((uint64_t)1 << live) - 1 : 0;
+        if (!evi) okm = 0;
+#pragma unroll
+        for (int q = 0; q < NI / 8; q++) mem[e][wc0 / 8 + q] = (uint8_t)(okm >> (8 * q));
+        if (ovm & okm) e_ovf[e] = 1;
+    }
+    __syncthreads();
+    // phase 2: one wave per event
+    for (int e2 = wave; e2 < TP; e2 += NW) {
+        if (e_row[e2] < 0) continue;   // wave-uniform
+        bool ok[CPL];
+        int m = 0;
+#pragma unroll
+        for (int q = 0; q < CPL; q++) {
+            const int c = lane + 64 * q;
+            ok[q] = (mem[e2][c >> 3] >> (c & 7)) & 1u;
+            m += __popcll(__ballot(ok[q]));
+        }
+        int64_t res;
+        if (!e_ovf[e2]) {
+            uint32_t v[CPL];
+#pragma unroll
+            for (int q = 0; q < CPL; q++) v[q] = vals[(lane + 64 * q) * LD + e2];
+            const uint32_t u = wave_select_kth32<CPL>(v, ok, m / 2, whist);
+            res = e_ts[e2] + (int64_t)(int32_t)(u ^ 0x80000000u);
+        } else {   // rare: offsets beyond 32 bits -> regather and select in 64 bits
+            uint64_t v[CPL];
+#pragma unroll
+            for (int q = 0; q < CPL; q++) {
+                const int c = lane + 64 * q;
+                int64_t x = 0;
+                if (ok[q]) x = p_ts[c_off[gb + c] - c_base[gb + c] + Coord<CT>::fd(FDT[(size_t)c * Pcap + ps + e2])];
+                v[q] = (uint64_t)x ^ 0x8000000000000000ull;
+            }
+            res = (int64_t)(wave_select_kth<CPL>(v, ok, m / 2, whist) ^ 0x8000000000000000ull);
+        }
+        if (lane == 0) p_cts[ps + e2] = res;
+    }
+}
+
+template <int NPAD, typename CT>
+static bool cts_row_launch(hipStream_t s, const DevArrays& a, int c_lo, int c_cnt, int C, int n, int64_t P,
+                           int max_cnt, int R, int k_rows) {
+    constexpr int TP = kRowTP, NW = row_waves(NPAD);
+    // two blocks per CU at NPAD = 256: the block's static LDS, vals and the staged rows within 79 KB
+    constexpr size_t kStatic = (size_t)TP * (NPAD / 8) + (size_t)TP * 16 + 4 * NW;
+    const size_t fixed = (size_t)NPAD * (TP + 1) * 4, row = (size_t)(n + 1) * 4;
+    const int room = (int)(((size_t)79 * 1024 - kStatic - fixed) / row);
+    const int K = k_rows > 0 ? std::min(k_rows, kRowKMax) : std::max(1, std::min(room, kRowKMax));
+    const size_t lds = fixed + std::max((size_t)K * row, (size_t)NW * 1024);   // (the rows' space is the histograms' in phase 2)
+    const void* f = (const void*)k_cts_row<NPAD, CT, TP, kRowD, NW>;
+    if (ensure_lds_limit(f, lds) != hipSuccess) return false;
+    const int64_t blocks = (int64_t)c_cnt * ((max_cnt + 31 + TP - 1) / TP);   // (a first tile starts up to 31 positions early)
+    if (blocks > 0x7FFFFFFF) return false;
+    hipLaunchKernelGGL((k_cts_row<NPAD, CT, TP, kRowD, NW>), dim3((unsigned)blocks), dim3(64 * NW), lds, s, a.fu, a.rcnt, a.p_rr,
+                       a.c_off, a.c_base, a.WLAT, (const CT*)a.FDT, a.p_ts, a.p_cts, C, n, P, c_lo, c_cnt, R, K);
+    return true;
+}
+
+template <typename CT>
+static bool launch_cts_row_t(hipStream_t s, const DevArrays& a, int c_lo, int c_cnt, int C, int n, int64_t P,
+                             int max_cnt, int R, int k_rows) {
+    if (n <= 64) return cts_row_launch<64, CT>(s, a, c_lo, c_cnt, C, n, P, max_cnt, R, k_rows);
+    if (n <= 128) return cts_row_launch<128, CT>(s, a, c_lo, c_cnt, C, n, P, max_cnt, R, k_rows);
+    return cts_row_launch<256, CT>(s, a, c_lo, c_cnt, C, n, P, max_cnt, R, k_rows);
+}
+
+bool cts_row_ok(int n) { return n > 32 && n <= 256; }
+int cts_row_tile() { return kRowTP; }
+
+bool launch_cts_row(hipStream_t s, const DevArrays& a, int c_lo, int c_cnt, int C, int n, int64_t P, int max_cnt,
+                    int R, int k_rows) {
+    if (max_cnt <= 0 || c_cnt <= 0) return true;
+    if (!cts_row_ok(n) || R <= 0) return false;
+    return a.compact ? launch_cts_row_t<uint16_t>(s, a, c_lo, c_cnt, C, n, P, max_cnt, R, k_rows)
+                     : launch_cts_row_t<int32_t>(s, a, c_lo, c_cnt, C, n, P, max_cnt, R, k_rows);
+}
+
 }  // namespace hgx

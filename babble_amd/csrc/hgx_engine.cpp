@@ -2294,11 +2294,22 @@ hipError_t Engine::find_order_begin(const std::vector<uint8_t>& el, const std::v
         fo_m = 0;
         return collect_kernel_times();
     }
-    kbeg(K_CTS);
-    if (cts_kernel != 2 || !launch_cts_pipe(stream, a, shard_lo, shard_hi - shard_lo, C, n, fd_ld, max_cnt))
-        launch_cts(stream, a, shard_lo, shard_hi - shard_lo, C, n, fd_ld, max_cnt);
     int64_t own = 0;
     for (int c = shard_lo; c < shard_hi; c++) own += fo_cnt[c];
+    const int c_cnt = shard_hi - shard_lo;
+    // auto: the lane = event kernel where a launched chain receives at least 8 tiles (512 events) on
+    // average. Measured at n = 256: from 16 to 256 events per chain its few large
+    // blocks do not fill the device and k_cts_tile is 1-6 us ahead, from about 1 000 the two tie,
+    // from 2 000 it is ahead (3.5 %, 8 % at 39 000); a SyncLimit-sized call receives a handful per
+    // chain. Modes 3 / 4 force it wherever it has an instantiation
+    constexpr int kCtsRowMinTiles = 8;
+    const bool row = cts_row_ok(n) &&
+        (cts_kernel >= 3 || (cts_kernel == 0 && own >= (int64_t)kCtsRowMinTiles * cts_row_tile() * c_cnt));
+    kbeg(K_CTS);
+    if (row && launch_cts_row(stream, a, shard_lo, c_cnt, C, n, fd_ld, max_cnt, R, cts_kernel == 4 ? 1 : 0))
+        cts_row_runs++;
+    else if (cts_kernel != 2 || !launch_cts_pipe(stream, a, shard_lo, c_cnt, C, n, fd_ld, max_cnt))
+        launch_cts(stream, a, shard_lo, c_cnt, C, n, fd_ld, max_cnt);
     kend(K_CTS, (double)own * (4.0 * n + 8.0 * n));
     return hipSuccess;
 }

@@ -364,7 +364,9 @@ class Engine {
     int fame_tally = 0;       // launch_fame tally (hgx_set_fame_tally)
     int round_kernel = 0;     // hgx_set_round_kernel: 0 persistent recurrence on rebuilds where it applies (3: every call),
                               // else per-launch per-candidate steps; 1 block-search steps; 2 per-candidate steps
-    int cts_kernel = 1;       // hgx_set_cts_kernel: 1 per-tile blocks (default: measured faster), 2 pipelined (hgx_cts.hip)
+    int cts_kernel = 0;       // hgx_set_cts_kernel: 0 auto (lane = event blocks on calls that receive >= 8 tiles per
+                              // chain, else 1), 1 per-tile blocks, 2 pipelined, 3 lane = event, 4 the same with one staged row
+    int64_t cts_row_runs = 0; // FindOrders whose timestamps ran on k_cts_row
     int64_t round_g_runs = 0;   // whole-graph recurrence launches (n <= 16)
     // shard `shard` of a chain-sharded group (nullptr: not sharded)
     ShardGroup* grp = nullptr;

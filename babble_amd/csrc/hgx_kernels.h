@@ -300,6 +300,14 @@ void launch_cts(hipStream_t s, const DevArrays& a, int c_lo, int c_cnt, int C, i
 // it does not apply (cts_pipe_ok) and nothing was launched
 bool cts_pipe_ok(int n, int C);
 bool launch_cts_pipe(hipStream_t s, const DevArrays& a, int c_lo, int c_cnt, int C, int n, int64_t P, int max_cnt);
+// the same, lane = event (hgx_cts.hip, k_cts_row): blocks of cts_row_tile() positions of one chain,
+// whole firstDescendants lines per load; n in (32, 256] (cts_row_ok). R = rounds of WLAT;
+// k_rows = WLAT rows staged per block (0: as many as the LDS budget allows). false when it does
+// not apply and nothing was launched
+bool cts_row_ok(int n);
+int cts_row_tile();
+bool launch_cts_row(hipStream_t s, const DevArrays& a, int c_lo, int c_cnt, int C, int n, int64_t P, int max_cnt,
+                    int R, int k_rows);
 // shard exchange: consensus timestamps of the newly received events of chains [lo, hi) to /
 // from a chain-major buffer (offs[c] = start of chain c)
 void launch_cts_shard_copy(hipStream_t s, const DevArrays& a, int lo, int hi, const int32_t* offs, int64_t* buf,

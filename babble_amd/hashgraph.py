@@ -910,8 +910,8 @@ class Hashgraph:
                     pending_loaded=self.PendingLoadedEvents(graph), blocks=self.Blocks(graph))
 
     def phase_times(self):
-        out = np.zeros(27, np.float64)
-        self.L.hgx_phase_times(self.ctx, ptr(out), 27)
+        out = np.zeros(28, np.float64)
+        self.L.hgx_phase_times(self.ctx, ptr(out), 28)
         return dict(coords_ms=out[0], rounds_ms=out[1], fame_ms=out[2], order_ms=out[3],
                     la_sweeps=int(out[4]), rounds=int(out[5]), compact=int(out[6]),
                     la_rows=int(out[7]), rebuild=int(out[8]), r_lo=int(out[9]),
@@ -921,7 +921,7 @@ class Hashgraph:
                     round_g_runs=int(out[18]), la_small=int(out[19]), la_verify=int(out[20]),
                     sort_seg=int(out[21]), ingest_pieces=int(out[22]),
                     host_rounds_ms=out[23], host_fame_ms=out[24], host_order_ms=out[25],
-                    payload_end_ms=out[26])
+                    payload_end_ms=out[26], cts_row=int(out[27]))
 
     def set_ingest_pipeline(self, pieces, min_events=4_000_000):
         """insert_and_run of compact columns on an empty context: the structure columns in `pieces`
@@ -980,9 +980,13 @@ class Hashgraph:
             raise ValueError("hgx_set_shard_remote: not a chain-sharded context")
 
     def set_cts_kernel(self, mode):
-        """FindOrder consensus timestamps: "auto" = "tile" (default: one tile of 8 positions per
-        block) or "pipe" (resident blocks with several tiles' loads in flight, hgx_cts.hip)."""
-        m = {"auto": 0, "tile": 1, "pipe": 2}[mode] if isinstance(mode, str) else int(mode)
+        """FindOrder consensus timestamps: "auto" (default: "row" for 32 < n <= 256 on a call that
+        receives at least 512 events per chain, else "tile"; "auto" no longer equals "tile"), "tile"
+        (one tile of 8 positions per block), "pipe" (resident blocks with several tiles' loads in
+        flight, hgx_cts.hip), "row" (blocks of 64 positions, lane = event, on every call where
+        32 < n <= 256, else "tile") or "row1" ("row" with one staged WLAT row per block: the
+        global-memory membership path, for tests and measurement)."""
+        m = {"auto": 0, "tile": 1, "pipe": 2, "row": 3, "row1": 4}[mode] if isinstance(mode, str) else int(mode)
         if self.L.hgx_set_cts_kernel(self.ctx, m) != 0:
             raise ValueError(f"invalid timestamp kernel {mode}")
 

@@ -706,6 +706,8 @@ int32_t hgx_p256_verify_bench(int32_t device, const uint8_t* keys65, int32_t n_k
 /* ... then host wall clock (ms) of the last calls' host-only sections: the bookkeeping after
  * DivideRounds' device work, after DecideFame's, before and after FindOrder's, and the time the
  * payload commit of the last hgx_insert_and_run* took (up to 27 values) */
+/* ... then the FindOrders so far whose consensus timestamps ran on the lane = event kernel (k_cts_row)
+ * (up to 28 values) */
 int32_t hgx_phase_times(hgx_ctx* ctx, double* out, int32_t cap);
 /* dominant-kernel accounting for the roofline line of bench.py:
  * name of the kernel, summed device ms (the round steps time one hipGraph replay in four and
@@ -767,10 +769,15 @@ int32_t hgx_set_round_shards(hgx_ctx* ctx, int32_t shards);
  * peer path), also where the shards share a device, so a one-GPU box runs the instructions the
  * shards of an 8-GPU node run. HGX_ERR_INVALID on a context without shards. Same results. */
 int32_t hgx_set_shard_remote(hgx_ctx* ctx, int32_t on);
-/* FindOrder consensus timestamps: 0 = default = 1: one tile of 8 positions per block (k_cts_small /
- * k_cts_tile, hgx_kernels.hip); 2 = resident blocks with three tiles' loads in flight behind the
- * selects of a fourth (hgx_cts.hip) where it applies (32 < n <= 512, at most 4096 chains),
- * otherwise mode 1 (measured slower at c3: 12.6 against 8.9 ms). Same results. */
+/* FindOrder consensus timestamps: 0 = default: for 32 < n <= 256, blocks of 64 positions of one chain
+ * with lane = event and whole firstDescendants lines per load (k_cts_row, hgx_cts.hip) on a call
+ * that receives at least 512 events per launched chain, otherwise as 1; 1 = one tile of 8
+ * positions per block (k_cts_small / k_cts_tile, hgx_kernels.hip); 2 = resident blocks with three
+ * tiles' loads in flight behind the selects of a fourth (hgx_cts.hip) where it applies (32 < n <= 512,
+ * at most 4096 chains), otherwise mode 1 (measured slower at c3: 12.6 against 8.9 ms); 3 = k_cts_row
+ * on every call where it applies (32 < n <= 256), otherwise mode 1; 4 = mode 3 with one staged
+ * WLAT row per block, so most blocks read their membership rows from global memory (tests and
+ * measurement). Same results. */
 int32_t hgx_set_cts_kernel(hgx_ctx* ctx, int32_t mode);
 /* DivideRounds schedule: 1 = incremental (default: a call after more InsertEvents extends
  * lastAncestors/firstDescendants for the new events only and resumes the round steps at the
