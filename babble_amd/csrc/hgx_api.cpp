@@ -508,103 +508,120 @@ static int32_t finish_insert(hgx_ctx* c, const hgx::InsertOut& out, int64_t* n_i
     return rc;
 }
 
-static int32_t insert_events_one(hgx_ctx* c, const hgx_events* ev, int64_t count, int64_t* n_inserted, hgx_error* err) {
+// ---- the host column forms (include/hgx.h; hgx_ingest_cols.h is the one table of them) ----
+// The columns of an entry point's struct as the engine takes them. False (bad arguments): a NULL
+// struct, a negative count, a NULL column of a non-empty batch, a bad exception list.
+static bool cols_present(const hgx::HostCols& hc, int64_t count) {
+    if (count < 0) return false;
+    const hgx::FormSpec& fs = hgx::form_spec(hc.form);
+    for (int i = 0; i < fs.n && count > 0; i++)
+        if (fs.col[i].kind != hgx::kColException && !hc.col[fs.col[i].id]) return false;
+    return true;
+}
+
+static hgx::HostCols wide_cols(const int32_t* creator, const int64_t* index, const int64_t* sp, const int64_t* op,
+                               const int64_t* ts, const uint8_t* hash, const uint8_t* S, const int32_t* ntx,
+                               const int32_t* nil) {
+    hgx::HostCols hc{};
+    hc.form = hgx::Form::wide;
+    hc.col[hgx::kColCreator] = creator; hc.col[hgx::kColIndex] = index; hc.col[hgx::kColSp] = sp;
+    hc.col[hgx::kColOp] = op; hc.col[hgx::kColTs] = ts; hc.col[hgx::kColHash] = hash; hc.col[hgx::kColS] = S;
+    hc.col[hgx::kColNtx] = ntx; hc.col[hgx::kColNil] = nil;
+    return hc;
+}
+
+static bool host_cols(const hgx_events* ev, int64_t count, hgx::HostCols& hc) {
+    if (!ev) return false;
+    hc = wide_cols(ev->creator, ev->index, ev->self_parent, ev->other_parent, ev->timestamp_ns, ev->hash, ev->sig_s,
+                   ev->ntx, ev->tx_nil);
+    return cols_present(hc, count);
+}
+
+static bool host_cols(const hgx_events32* ev, int64_t count, hgx::HostCols& hc) {
+    if (!ev) return false;
+    hc = hgx::HostCols{};
+    hc.form = hgx::Form::compact;
+    hc.col[hgx::kColCreator] = ev->creator; hc.col[hgx::kColIndex32] = ev->index; hc.col[hgx::kColSp32] = ev->self_parent;
+    hc.col[hgx::kColOp32] = ev->other_parent; hc.col[hgx::kColTs] = ev->timestamp_ns; hc.col[hgx::kColCoin] = ev->coin;
+    hc.col[hgx::kColS] = ev->sig_s; hc.col[hgx::kColNtx] = ev->ntx;
+    return cols_present(hc, count);
+}
+
+// (10-byte structure columns, decoded on the device)
+static bool host_cols(const hgx_events_packed* ev, int64_t count, hgx::HostCols& hc) {
+    if (!ev) return false;
+    hc = hgx::HostCols{};
+    hc.form = hgx::Form::packed;
+    hc.n_exc = ev->n_exc;
+    hc.col[hgx::kColCreator16] = ev->creator; hc.col[hgx::kColIndex32] = ev->index;
+    hc.col[hgx::kColSpBack] = ev->self_parent_back; hc.col[hgx::kColOpBack] = ev->other_parent_back;
+    hc.col[hgx::kColExcPos] = ev->exc_pos; hc.col[hgx::kColExcSp] = ev->exc_self_parent;
+    hc.col[hgx::kColExcOp] = ev->exc_other_parent; hc.col[hgx::kColTs] = ev->timestamp_ns;
+    hc.col[hgx::kColCoin] = ev->coin; hc.col[hgx::kColS] = ev->sig_s; hc.col[hgx::kColNtx] = ev->ntx;
+    if (!cols_present(hc, count)) return false;
+    if (count == 0) return true;
+    if (ev->n_exc < 0 || ev->n_exc > count) return false;
+    if (ev->n_exc == 0) return true;
+    if (!ev->exc_pos || !ev->exc_self_parent || !ev->exc_other_parent) return false;
+    // the device scatters the exceptions unchecked: positions in the batch and distinct
+    std::vector<int64_t> p(ev->exc_pos, ev->exc_pos + ev->n_exc);
+    std::sort(p.begin(), p.end());
+    return p.front() >= 0 && p.back() < count && std::adjacent_find(p.begin(), p.end()) == p.end();
+}
+
+static int32_t insert_host_one(hgx_ctx* c, const hgx::HostCols& hc, int64_t count, int64_t* n_inserted, hgx_error* err,
+                               const char* who) {
     if (n_inserted) *n_inserted = 0;
-    if (!c || !ev || count < 0 ||
-        (count > 0 && (!ev->creator || !ev->index || !ev->self_parent || !ev->other_parent || !ev->timestamp_ns ||
-                       !ev->hash || !ev->sig_s || !ev->ntx || !ev->tx_nil))) {
-        set_err(err, HGX_ERR_INVALID, "hgx_insert_events: bad arguments");
+    if (hc.form != hgx::Form::wide && c->rooted) {
+        set_err(err, HGX_ERR_INVALID, std::string(who) + ": a reset context checks Root.Others by event id: use hgx_insert_events");
         return HGX_ERR_INVALID;
     }
     DeviceGuard dg(c);
     hgx::InsertIn in{};
     if (count > 0) {
-        hipError_t e = c->eng.stage_host(ev->creator, ev->index, ev->self_parent, ev->other_parent, ev->timestamp_ns,
-                                         ev->hash, ev->sig_s, ev->ntx, ev->tx_nil, count, in);
-        if (e != hipSuccess) return dev_err(err, e, "hgx_insert_events");
+        hipError_t e = c->eng.stage(hc, count, hgx::Engine::kStageAll, in);
+        if (e != hipSuccess) return dev_err(err, e, who);
     }
     hgx::InsertOut out;
     hipError_t e = c->eng.insert(in, count, out);
-    if (e != hipSuccess) return dev_err(err, e, "hgx_insert_events");
+    if (e != hipSuccess) return dev_err(err, e, who);
     return finish_insert(c, out, n_inserted, err);
 }
 
-// a chain-sharded context: every shard inserts the batch (each holds the whole DAG)
-int32_t hgx_insert_events(hgx_ctx* c, const hgx_events* ev, int64_t count, int64_t* n_inserted, hgx_error* err) {
-    if (c && c->grp)
+// hc: null = bad arguments (host_cols). A chain-sharded context: every shard inserts the batch (each
+// holds the whole DAG)
+static int32_t insert_host(hgx_ctx* c, const hgx::HostCols* hc, int64_t count, int64_t* n_inserted, hgx_error* err,
+                           const char* who) {
+    if (n_inserted) *n_inserted = 0;
+    if (!c || !hc) {
+        set_err(err, HGX_ERR_INVALID, std::string(who) + ": bad arguments");
+        return HGX_ERR_INVALID;
+    }
+    if (c->grp)
         return on_shards(c, err, [&](hgx_ctx* x, hgx_error* e) {
-            return insert_events_one(x, ev, count, x == c ? n_inserted : nullptr, e);
+            return insert_host_one(x, *hc, count, x == c ? n_inserted : nullptr, e, who);
         });
-    return insert_events_one(c, ev, count, n_inserted, err);
+    return insert_host_one(c, *hc, count, n_inserted, err, who);
 }
 
-static int32_t run_after_split(hgx_ctx* c, hgx::InsertOut& out, int64_t* n_inserted, hgx_error* err, const char* who);
-static int32_t divide_rounds_fused(hgx_ctx* c, hgx_error* err, int fuse);
-static int32_t decide_fame_one(hgx_ctx* c, hgx_error* err);
-
-// Bootstrap / Core.Sync + RunConsensus in one call (hashgraph.go:1008-1037, node/core.go:190-303):
-// InsertEvent for the batch, then DivideRounds, DecideFame and FindOrder. The insert is split
-// (Engine::insert_split_begin): the structure columns are validated and committed first, and
-// the payload columns (timestamps, hash, S, transactions: 80 of the 108 bytes per event) are
-// copied to HBM while DivideRounds runs, committed before DecideFame reads the coins.
-int32_t hgx_insert_and_run(hgx_ctx* c, const hgx_events* ev, int64_t count, int64_t* n_inserted, hgx_error* err) {
-    if (n_inserted) *n_inserted = 0;
-    if (!c || !ev || count < 0 ||
-        (count > 0 && (!ev->creator || !ev->index || !ev->self_parent || !ev->other_parent || !ev->timestamp_ns ||
-                       !ev->hash || !ev->sig_s || !ev->ntx || !ev->tx_nil))) {
-        set_err(err, HGX_ERR_INVALID, "hgx_insert_and_run: bad arguments");
-        return HGX_ERR_INVALID;
-    }
-    if (count < 65536 || c->rooted || c->shard_world > 1) {   // small batches gain nothing from the overlap
-        int32_t rc = hgx_insert_events(c, ev, count, n_inserted, err);
-        if (rc) return rc;
-        return hgx_run_consensus(c, err);
-    }
-    DeviceGuard dg(c);
-    hgx::InsertOut out;
-    hipError_t e = c->eng.insert_split_begin(ev->creator, ev->index, ev->self_parent, ev->other_parent, count, out);
-    if (e != hipSuccess) return dev_err(err, e, "hgx_insert_and_run");
-    e = c->eng.payload_begin(ev->timestamp_ns, ev->hash, ev->sig_s, ev->ntx, ev->tx_nil, out.accepted);
-    if (e != hipSuccess) return dev_err(err, e, "hgx_insert_and_run");
-    return run_after_split(c, out, n_inserted, err, "hgx_insert_and_run");
-}
-
-static bool bad_events32(const hgx_events32* ev, int64_t count) {
-    return !ev || count < 0 ||
-           (count > 0 && (!ev->creator || !ev->index || !ev->self_parent || !ev->other_parent || !ev->timestamp_ns ||
-                          !ev->coin || !ev->sig_s || !ev->ntx));
-}
-
-static int32_t insert_events32_one(hgx_ctx* c, const hgx_events32* ev, int64_t count, int64_t* n_inserted, hgx_error* err) {
-    if (n_inserted) *n_inserted = 0;
-    if (!c || bad_events32(ev, count)) {
-        set_err(err, HGX_ERR_INVALID, "hgx_insert_events32: bad arguments");
-        return HGX_ERR_INVALID;
-    }
-    if (c->rooted) {
-        set_err(err, HGX_ERR_INVALID, "hgx_insert_events32: a reset context checks Root.Others by event id: use hgx_insert_events");
-        return HGX_ERR_INVALID;
-    }
-    DeviceGuard dg(c);
-    hgx::InsertIn in{};
-    if (count > 0) {
-        hipError_t e = c->eng.stage_host32(ev->creator, ev->index, ev->self_parent, ev->other_parent, ev->timestamp_ns,
-                                           ev->coin, ev->sig_s, ev->ntx, count, in);
-        if (e != hipSuccess) return dev_err(err, e, "hgx_insert_events32");
-    }
-    hgx::InsertOut out;
-    hipError_t e = c->eng.insert(in, count, out);
-    if (e != hipSuccess) return dev_err(err, e, "hgx_insert_events32");
-    return finish_insert(c, out, n_inserted, err);
+int32_t hgx_insert_events(hgx_ctx* c, const hgx_events* ev, int64_t count, int64_t* n_inserted, hgx_error* err) {
+    hgx::HostCols hc;
+    return insert_host(c, host_cols(ev, count, hc) ? &hc : nullptr, count, n_inserted, err, "hgx_insert_events");
 }
 
 int32_t hgx_insert_events32(hgx_ctx* c, const hgx_events32* ev, int64_t count, int64_t* n_inserted, hgx_error* err) {
-    if (c && c->grp)
-        return on_shards(c, err, [&](hgx_ctx* x, hgx_error* e) {
-            return insert_events32_one(x, ev, count, x == c ? n_inserted : nullptr, e);
-        });
-    return insert_events32_one(c, ev, count, n_inserted, err);
+    hgx::HostCols hc;
+    return insert_host(c, host_cols(ev, count, hc) ? &hc : nullptr, count, n_inserted, err, "hgx_insert_events32");
 }
+
+int32_t hgx_insert_events_packed(hgx_ctx* c, const hgx_events_packed* ev, int64_t count, int64_t* n_inserted,
+                                 hgx_error* err) {
+    hgx::HostCols hc;
+    return insert_host(c, host_cols(ev, count, hc) ? &hc : nullptr, count, n_inserted, err, "hgx_insert_events_packed");
+}
+
+static int32_t divide_rounds_fused(hgx_ctx* c, hgx_error* err, int fuse);
+static int32_t decide_fame_one(hgx_ctx* c, hgx_error* err);
 
 // the rest of an insert_and_run once the structure is committed and the payload copy started
 // (hgx_insert_and_run, hgx_insert_and_run32 / _packed): DivideRounds beside the copy, then DecideFame,
@@ -663,119 +680,69 @@ static int32_t run_after_split(hgx_ctx* c, hgx::InsertOut& out, int64_t* n_inser
     return ok(err);
 }
 
-// hgx_insert_and_run with the compact columns: the structure columns (16 bytes per event) are
-// validated and committed first, the payload (45 bytes) copied beside DivideRounds
-int32_t hgx_insert_and_run32(hgx_ctx* c, const hgx_events32* ev, int64_t count, int64_t* n_inserted, hgx_error* err) {
+// Bootstrap / Core.Sync + RunConsensus in one call (hashgraph.go:1008-1037, node/core.go:190-303):
+// InsertEvent for the batch, then DivideRounds, DecideFame and FindOrder. The insert is split
+// (Engine::insert_split_begin): the structure columns (28, 16 or 10 of the 108, 61 or 55 bytes per
+// event) are validated and committed first, and the payload columns (timestamps, hash or coin, S,
+// transactions) are copied to HBM while DivideRounds runs, committed before DecideFame reads the
+// coins. who_insert: the form's plain insert, which small batches and rooted or row-sharded contexts
+// take instead.
+static int32_t insert_and_run_host(hgx_ctx* c, const hgx::HostCols* hc, int64_t count, int64_t* n_inserted,
+                                   hgx_error* err, const char* who, const char* who_insert) {
     if (n_inserted) *n_inserted = 0;
-    if (!c || bad_events32(ev, count)) {
-        set_err(err, HGX_ERR_INVALID, "hgx_insert_and_run32: bad arguments");
+    if (!c || !hc) {
+        set_err(err, HGX_ERR_INVALID, std::string(who) + ": bad arguments");
         return HGX_ERR_INVALID;
     }
-    c->eng.pipe_used = 0;
-    if (count < 65536 || c->rooted || c->shard_world > 1) {
-        int32_t rc = hgx_insert_events32(c, ev, count, n_inserted, err);
+    const bool compact = hc->form == hgx::Form::compact;
+    if (compact) c->eng.pipe_used = 0;
+    if (count < 65536 || c->rooted || c->shard_world > 1) {   // small batches gain nothing from the overlap
+        int32_t rc = insert_host(c, hc, count, n_inserted, err, who_insert);
         if (rc) return rc;
         return hgx_run_consensus(c, err);
     }
     DeviceGuard dg(c);
     hgx::InsertOut out;
-    // a large first batch: inserted, laid out and its lastAncestors started piece by piece while the
-    // later columns still cross PCIe; otherwise, or after a failed check, as before
+    // a large first batch of compact columns: inserted, laid out and its lastAncestors started piece
+    // by piece while the later columns still cross PCIe; otherwise, or after a failed
+    // check, the serial split
     bool piped = false;
-    hipError_t e = c->grp ? hipSuccess
-                          : c->eng.insert_pipe32(ev->creator, ev->index, ev->self_parent, ev->other_parent,
-                                                 ev->timestamp_ns, ev->coin, ev->sig_s, ev->ntx, count, out, piped);
-    if (e != hipSuccess) return dev_err(err, e, "hgx_insert_and_run32");
+    hipError_t e = compact && !c->grp ? c->eng.insert_pipe32(*hc, count, out, piped) : hipSuccess;
+    if (e != hipSuccess) return dev_err(err, e, who);
     if (!piped) {   // (the pipeline's copier goes on with the payload itself)
-        e = c->eng.insert_split_begin32(ev->creator, ev->index, ev->self_parent, ev->other_parent, count, out);
-        if (e != hipSuccess) return dev_err(err, e, "hgx_insert_and_run32");
-        e = c->eng.payload_begin32(ev->timestamp_ns, ev->coin, ev->sig_s, ev->ntx, out.accepted);
-        if (e != hipSuccess) return dev_err(err, e, "hgx_insert_and_run32");
+        e = c->eng.insert_split_begin(*hc, count, out);
+        if (e != hipSuccess) return dev_err(err, e, who);
+        e = c->eng.payload_begin(*hc, out.accepted);
+        if (e != hipSuccess) return dev_err(err, e, who);
     }
-    return run_after_split(c, out, n_inserted, err, "hgx_insert_and_run32");
+    return run_after_split(c, out, n_inserted, err, who);
 }
 
-// ---- hgx_events_packed (include/hgx.h): 10-byte structure columns, decoded on the device ----
-static bool bad_packed(const hgx_events_packed* ev, int64_t count) {
-    if (!ev || count < 0) return true;
-    if (count == 0) return false;
-    if (!ev->creator || !ev->index || !ev->self_parent_back || !ev->other_parent_back || !ev->timestamp_ns ||
-        !ev->coin || !ev->sig_s || !ev->ntx || ev->n_exc < 0 || ev->n_exc > count)
-        return true;
-    if (ev->n_exc == 0) return false;
-    if (!ev->exc_pos || !ev->exc_self_parent || !ev->exc_other_parent) return true;
-    // the device scatters the exceptions unchecked: positions in the batch and distinct
-    std::vector<int64_t> p(ev->exc_pos, ev->exc_pos + ev->n_exc);
-    std::sort(p.begin(), p.end());
-    return p.front() < 0 || p.back() >= count || std::adjacent_find(p.begin(), p.end()) != p.end();
+int32_t hgx_insert_and_run(hgx_ctx* c, const hgx_events* ev, int64_t count, int64_t* n_inserted, hgx_error* err) {
+    hgx::HostCols hc;
+    return insert_and_run_host(c, host_cols(ev, count, hc) ? &hc : nullptr, count, n_inserted, err, "hgx_insert_and_run",
+                               "hgx_insert_events");
 }
 
-static hgx::Engine::Packed packed_of(const hgx_events_packed* ev) {
-    return hgx::Engine::Packed{ev->creator, ev->index, ev->self_parent_back, ev->other_parent_back,
-                               ev->n_exc, ev->exc_pos, ev->exc_self_parent, ev->exc_other_parent};
+int32_t hgx_insert_and_run32(hgx_ctx* c, const hgx_events32* ev, int64_t count, int64_t* n_inserted, hgx_error* err) {
+    hgx::HostCols hc;
+    return insert_and_run_host(c, host_cols(ev, count, hc) ? &hc : nullptr, count, n_inserted, err,
+                               "hgx_insert_and_run32", "hgx_insert_events32");
 }
 
-static int32_t insert_events_packed_one(hgx_ctx* c, const hgx_events_packed* ev, int64_t count, int64_t* n_inserted,
-                                        hgx_error* err) {
-    if (n_inserted) *n_inserted = 0;
-    if (c->rooted) {
-        set_err(err, HGX_ERR_INVALID, "hgx_insert_events_packed: a reset context checks Root.Others by event id: use hgx_insert_events");
-        return HGX_ERR_INVALID;
-    }
-    DeviceGuard dg(c);
-    hgx::InsertIn in{};
-    if (count > 0) {
-        hipError_t e = c->eng.stage_packed(packed_of(ev), count, in, ev->timestamp_ns, ev->coin, ev->sig_s, ev->ntx);
-        if (e != hipSuccess) return dev_err(err, e, "hgx_insert_events_packed");
-    }
-    hgx::InsertOut out;
-    hipError_t e = c->eng.insert(in, count, out);
-    if (e != hipSuccess) return dev_err(err, e, "hgx_insert_events_packed");
-    return finish_insert(c, out, n_inserted, err);
-}
-
-int32_t hgx_insert_events_packed(hgx_ctx* c, const hgx_events_packed* ev, int64_t count, int64_t* n_inserted,
-                                 hgx_error* err) {
-    if (n_inserted) *n_inserted = 0;
-    if (!c || bad_packed(ev, count)) {
-        set_err(err, HGX_ERR_INVALID, "hgx_insert_events_packed: bad arguments");
-        return HGX_ERR_INVALID;
-    }
-    if (c->grp)
-        return on_shards(c, err, [&](hgx_ctx* x, hgx_error* e) {
-            return insert_events_packed_one(x, ev, count, x == c ? n_inserted : nullptr, e);
-        });
-    return insert_events_packed_one(c, ev, count, n_inserted, err);
-}
-
-// hgx_insert_and_run32 with the packed structure columns: 10 bytes per event staged, decoded and
-// validated before DivideRounds, the payload (45 bytes) copied beside it as in hgx_insert_and_run32
 int32_t hgx_insert_and_run_packed(hgx_ctx* c, const hgx_events_packed* ev, int64_t count, int64_t* n_inserted,
                                   hgx_error* err) {
-    if (n_inserted) *n_inserted = 0;
-    if (!c || bad_packed(ev, count)) {
-        set_err(err, HGX_ERR_INVALID, "hgx_insert_and_run_packed: bad arguments");
-        return HGX_ERR_INVALID;
-    }
-    if (count < 65536 || c->rooted || c->shard_world > 1) {
-        int32_t rc = hgx_insert_events_packed(c, ev, count, n_inserted, err);
-        if (rc) return rc;
-        return hgx_run_consensus(c, err);
-    }
-    DeviceGuard dg(c);
-    hgx::InsertOut out;
-    hipError_t e = c->eng.insert_split_begin_packed(packed_of(ev), count, out);
-    if (e != hipSuccess) return dev_err(err, e, "hgx_insert_and_run_packed");
-    e = c->eng.payload_begin32(ev->timestamp_ns, ev->coin, ev->sig_s, ev->ntx, out.accepted);
-    if (e != hipSuccess) return dev_err(err, e, "hgx_insert_and_run_packed");
-    return run_after_split(c, out, n_inserted, err, "hgx_insert_and_run_packed");
+    hgx::HostCols hc;
+    return insert_and_run_host(c, host_cols(ev, count, hc) ? &hc : nullptr, count, n_inserted, err,
+                               "hgx_insert_and_run_packed", "hgx_insert_events_packed");
 }
 
 int32_t hgx_pack_events32(const hgx_events32* ev, int64_t count, int64_t base, uint16_t* creator16, uint16_t* sp_back,
                           uint16_t* op_back, int64_t* exc_pos, int32_t* exc_sp, int32_t* exc_op, int64_t exc_cap,
                           int64_t* n_exc, hgx_error* err) {
     if (n_exc) *n_exc = 0;
-    if (bad_events32(ev, count) || base < 0 || exc_cap < 0 || !n_exc ||
+    hgx::HostCols hc;
+    if (!host_cols(ev, count, hc) || base < 0 || exc_cap < 0 || !n_exc ||
         (count > 0 && (!creator16 || !sp_back || !op_back)) || (exc_cap > 0 && (!exc_pos || !exc_sp || !exc_op))) {
         set_err(err, HGX_ERR_INVALID, "hgx_pack_events32: bad arguments");
         return HGX_ERR_INVALID;
@@ -843,9 +810,8 @@ static int32_t insert_verified(hgx_ctx* c, const hgx_events* ev, const uint8_t* 
                                int64_t count, int64_t* n_inserted, hgx_error* err, bool on_device) {
     const char* who = on_device ? "hgx_insert_events_verified_device" : "hgx_insert_events_verified";
     if (n_inserted) *n_inserted = 0;
-    if (!c || !ev || count < 0 ||
-        (count > 0 && (!ev->creator || !ev->index || !ev->self_parent || !ev->other_parent || !ev->timestamp_ns ||
-                       !ev->hash || !ev->sig_s || !ev->ntx || !ev->tx_nil || !digest32 || !sig_r32)) ||
+    hgx::HostCols hc;
+    if (!c || !host_cols(ev, count, hc) || (count > 0 && (!digest32 || !sig_r32)) ||
         (on_device && (((uintptr_t)ev->sig_s & 15) || ((uintptr_t)ev->hash & 15)))) {
         set_err(err, HGX_ERR_INVALID, std::string(who) + ": bad arguments");
         return HGX_ERR_INVALID;
@@ -862,8 +828,7 @@ static int32_t insert_verified(hgx_ctx* c, const hgx_events* ev, const uint8_t* 
         in.creator = ev->creator; in.index = ev->index; in.sp = ev->self_parent; in.op = ev->other_parent;
         in.ts = ev->timestamp_ns; in.hash = ev->hash; in.S = ev->sig_s; in.ntx = ev->ntx; in.nil = ev->tx_nil;
     } else if (count > 0) {
-        hipError_t e = c->eng.stage_host(ev->creator, ev->index, ev->self_parent, ev->other_parent, ev->timestamp_ns,
-                                         ev->hash, ev->sig_s, ev->ntx, ev->tx_nil, count, in);
+        hipError_t e = c->eng.stage(hc, count, hgx::Engine::kStageAll, in);
         if (e == hipSuccess) e = c->eng.stage_sig(digest32, sig_r32, count, &dd, &dr);
         if (e != hipSuccess) return dev_err(err, e, who);
     }
@@ -920,8 +885,9 @@ int32_t hgx_insert_event_bodies_ext(hgx_ctx* c, const hgx_event_bodies* evb, con
         const uint8_t zero[32] = {};
         const int32_t ntx = evb->ntx[cut] < 0 ? 0 : evb->ntx[cut], nil = evb->ntx[cut] < 0 ? 1 : 0;
         hgx::InsertIn in{};
-        e = c->eng.stage_host(ev.creator + cut, ev.index + cut, ev.sp + cut, ev.op + cut, ev.ts + cut, zero,
-                              ev.s + 32 * cut, &ntx, &nil, 1, in);
+        e = c->eng.stage(wide_cols(ev.creator + cut, ev.index + cut, ev.sp + cut, ev.op + cut, ev.ts + cut, zero,
+                                   ev.s + 32 * cut, &ntx, &nil),
+                         1, hgx::Engine::kStageAll, in);
         if (e == hipSuccess) e = c->eng.insert(in, 1, out);
         if (e != hipSuccess) return dev_err(err, e, "hgx_insert_event_bodies");
         if (out.code == hgx::INS_OK) c->eng.ids_known = false;   // (unreachable: the event was stored without an id)
@@ -1071,10 +1037,8 @@ int32_t hgx_insert_wire_bodies(hgx_ctx* c, const hgx_wire_bodies* w, int64_t cou
 static int32_t insert_events_device_one(hgx_ctx* c, const hgx_events* ev, int64_t count, int64_t* n_inserted,
                                         hgx_error* err) {
     if (n_inserted) *n_inserted = 0;
-    if (!c || !ev || count < 0 ||
-        (count > 0 && (!ev->creator || !ev->index || !ev->self_parent || !ev->other_parent || !ev->timestamp_ns ||
-                       !ev->hash || !ev->sig_s || !ev->ntx || !ev->tx_nil)) ||
-        ((uintptr_t)ev->sig_s & 15) || ((uintptr_t)ev->hash & 15)) {
+    hgx::HostCols hc;   // (device pointers: the NULL checks alone)
+    if (!c || !host_cols(ev, count, hc) || ((uintptr_t)ev->sig_s & 15) || ((uintptr_t)ev->hash & 15)) {
         set_err(err, HGX_ERR_INVALID, "hgx_insert_events_device: bad arguments (hash / sig_s must be 16-byte aligned)");
         return HGX_ERR_INVALID;
     }

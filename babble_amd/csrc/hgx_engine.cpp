@@ -477,20 +477,63 @@ InsertState Engine::insert_state() {
 }
 
 template <typename T>
-static hipError_t stage_col(DBuf<T>& b, const T* src, size_t count, size_t per, hipStream_t s) {
-    if (b.n < count * per) HGX_TRY(b.alloc(count * per));
-    return hipMemcpyAsync(b.p, src, count * per * sizeof(T), hipMemcpyHostToDevice, s);
+static hipError_t reserve_bytes(DBuf<T>& b, size_t bytes, void*& p) {
+    if (b.n < bytes / sizeof(T)) HGX_TRY(b.alloc(bytes / sizeof(T)));
+    p = b.p;
+    return hipSuccess;
 }
 
-// a sync-sized batch (at most kPackEvents): the k host columns packed into pinned memory and sent as
-// one copy into st_pack (k pageable copies cost a staged, blocking transfer each); off[i] = column i's
-// byte offset in st_pack
-hipError_t Engine::stage_pinned(int k, const void* const* src, const size_t* bytes, size_t* off) {
-    size_t total = 0;
-    for (int i = 0; i < k; i++) {
-        off[i] = total;
-        total += (bytes[i] + 255) & ~(size_t)255;
+hipError_t Engine::stage_buf(ColId id, size_t bytes, void*& p) {
+    switch (id) {
+        case kColCreator: return reserve_bytes(st_creator, bytes, p);
+        case kColIndex: return reserve_bytes(st_index, bytes, p);
+        case kColSp: return reserve_bytes(st_sp, bytes, p);
+        case kColOp: return reserve_bytes(st_op, bytes, p);
+        case kColTs: return reserve_bytes(st_ts, bytes, p);
+        case kColHash: return reserve_bytes(st_hash, bytes, p);
+        case kColS: return reserve_bytes(st_S, bytes, p);
+        case kColNtx: return reserve_bytes(st_ntx, bytes, p);
+        case kColNil: return reserve_bytes(st_nil, bytes, p);
+        case kColIndex32: return reserve_bytes(st_index32, bytes, p);
+        case kColSp32: return reserve_bytes(st_sp32, bytes, p);
+        case kColOp32: return reserve_bytes(st_op32, bytes, p);
+        case kColCoin: return reserve_bytes(st_coin, bytes, p);
+        case kColCreator16: return reserve_bytes(st_c16, bytes, p);
+        case kColSpBack: return reserve_bytes(st_spb, bytes, p);
+        case kColOpBack: return reserve_bytes(st_opb, bytes, p);
+        case kColExcPos: return reserve_bytes(st_exc_pos, bytes, p);
+        case kColExcSp: return reserve_bytes(st_exc_sp, bytes, p);
+        case kColExcOp: return reserve_bytes(st_exc_op, bytes, p);
+        default: return hipErrorInvalidValue;
     }
+}
+
+// the InsertIn field of a column staged at p (the packed structure has none: it is decoded first)
+static void set_col(InsertIn& in, ColId id, const void* p) {
+    switch (id) {
+        case kColCreator: in.creator = (const int32_t*)p; break;
+        case kColIndex: in.index = (const int64_t*)p; break;
+        case kColSp: in.sp = (const int64_t*)p; break;
+        case kColOp: in.op = (const int64_t*)p; break;
+        case kColTs: in.ts = (const int64_t*)p; break;
+        case kColHash: in.hash = (const uint8_t*)p; break;
+        case kColS: in.S = (const uint8_t*)p; break;
+        case kColNtx: in.ntx = (const int32_t*)p; break;
+        case kColNil: in.nil = (const int32_t*)p; break;
+        case kColIndex32: in.index32 = (const int32_t*)p; break;
+        case kColSp32: in.sp32 = (const int32_t*)p; break;
+        case kColOp32: in.op32 = (const int32_t*)p; break;
+        case kColCoin: in.coin = (const uint8_t*)p; break;
+        default: break;
+    }
+}
+
+// a sync-sized batch (at most kPackEvents): the host columns packed into pinned memory and sent as
+// one copy into st_pack (a pageable copy per column costs a staged, blocking transfer each); off[i] =
+// byte offset in st_pack of the form's column i
+hipError_t Engine::stage_pinned(const HostCols& hc, int64_t count, size_t* off) {
+    const FormSpec& fs = form_spec(hc.form);
+    const size_t total = one_copy_layout(fs, count, hc.n_exc, off);
     if (st_pack.n < total) HGX_TRY(st_pack.alloc(std::max(total, (size_t)2 * st_pack.n)));
     if (h_pack_cap < total) {   // (every insert synchronized before returning: the buffer is free)
         if (h_pack) (void)hipHostFree(h_pack);
@@ -499,69 +542,57 @@ hipError_t Engine::stage_pinned(int k, const void* const* src, const size_t* byt
         HGX_TRY(hipHostMalloc((void**)&h_pack, std::max(total, (size_t)2 * st_pack.n), hipHostMallocDefault));
         h_pack_cap = std::max(total, (size_t)2 * st_pack.n);
     }
-    for (int i = 0; i < k; i++)
-        if (bytes[i]) std::memcpy(h_pack + off[i], src[i], bytes[i]);
+    for (int i = 0; i < fs.n; i++)
+        if (const size_t bytes = col_bytes(fs.col[i], count, hc.n_exc))
+            std::memcpy(h_pack + off[i], hc.col[fs.col[i].id], bytes);
     return hipMemcpyAsync(st_pack.p, h_pack, total, hipMemcpyHostToDevice, stream);
 }
 
-hipError_t Engine::stage_host(const int32_t* creator, const int64_t* index, const int64_t* sp, const int64_t* op,
-                              const int64_t* ts, const uint8_t* hash, const uint8_t* S, const int32_t* ntx,
-                              const int32_t* nil, int64_t count, InsertIn& in) {
-    const size_t c = (size_t)count;
-    if (count <= kPackEvents) {
-        const void* src[9] = {creator, index, sp, op, ts, hash, S, ntx, nil};
-        const size_t bytes[9] = {4 * c, 8 * c, 8 * c, 8 * c, 8 * c, 32 * c, 32 * c, 4 * c, 4 * c};
-        size_t off[9];
-        HGX_TRY(stage_pinned(9, src, bytes, off));
-        uint8_t* d = st_pack.p;
-        in.creator = (const int32_t*)(d + off[0]); in.index = (const int64_t*)(d + off[1]);
-        in.sp = (const int64_t*)(d + off[2]); in.op = (const int64_t*)(d + off[3]); in.ts = (const int64_t*)(d + off[4]);
-        in.hash = d + off[5]; in.S = d + off[6]; in.ntx = (const int32_t*)(d + off[7]); in.nil = (const int32_t*)(d + off[8]);
-        return hipSuccess;
-    }
-    HGX_TRY(stage_col(st_creator, creator, c, 1, stream));
-    HGX_TRY(stage_col(st_index, index, c, 1, stream));
-    HGX_TRY(stage_col(st_sp, sp, c, 1, stream));
-    HGX_TRY(stage_col(st_op, op, c, 1, stream));
-    HGX_TRY(stage_col(st_ts, ts, c, 1, stream));
-    HGX_TRY(stage_col(st_hash, hash, c, 32, stream));
-    HGX_TRY(stage_col(st_S, S, c, 32, stream));
-    HGX_TRY(stage_col(st_ntx, ntx, c, 1, stream));
-    HGX_TRY(stage_col(st_nil, nil, c, 1, stream));
-    in.creator = st_creator.p; in.index = st_index.p; in.sp = st_sp.p; in.op = st_op.p; in.ts = st_ts.p;
-    in.hash = st_hash.p; in.S = st_S.p; in.ntx = st_ntx.p; in.nil = st_nil.p;
-    return hipSuccess;
-}
-
-hipError_t Engine::stage_host32(const int32_t* creator, const int32_t* index, const int32_t* sp, const int32_t* op,
-                                const int64_t* ts, const uint8_t* coin, const uint8_t* S, const int32_t* ntx,
-                                int64_t count, InsertIn& in) {
-    const size_t c = (size_t)count;
+hipError_t Engine::stage(const HostCols& hc, int64_t count, StagePart part, InsertIn& in) {
+    const FormSpec& fs = form_spec(hc.form);
+    const bool packed = hc.form == Form::packed, one_copy = part == kStageAll && count <= kPackEvents;
+    const void* at[kNumCols] = {};   // where each column landed
+    void* p = nullptr;
     in = InsertIn{};
-    if (count <= kPackEvents) {   // one pinned packed copy (as stage_host)
-        const void* src[8] = {creator, index, sp, op, ts, coin, S, ntx};
-        const size_t bytes[8] = {4 * c, 4 * c, 4 * c, 4 * c, 8 * c, c, 32 * c, 4 * c};
-        size_t off[8];
-        HGX_TRY(stage_pinned(8, src, bytes, off));
-        uint8_t* d = st_pack.p;
-        in.creator = (const int32_t*)(d + off[0]); in.index32 = (const int32_t*)(d + off[1]);
-        in.sp32 = (const int32_t*)(d + off[2]); in.op32 = (const int32_t*)(d + off[3]);
-        in.ts = (const int64_t*)(d + off[4]); in.coin = d + off[5]; in.S = d + off[6];
-        in.ntx = (const int32_t*)(d + off[7]);
-        if (count > 0) ids_known = false;
-        return hipSuccess;
+    if (packed) {   // the decoded columns
+        HGX_TRY(stage_buf(kColCreator, (size_t)count * 4, p));
+        HGX_TRY(stage_buf(kColSp32, (size_t)count * 4, p));
+        HGX_TRY(stage_buf(kColOp32, (size_t)count * 4, p));
     }
-    HGX_TRY(stage_col(st_creator, creator, c, 1, stream));
-    HGX_TRY(stage_col(st_index32, index, c, 1, stream));
-    HGX_TRY(stage_col(st_sp32, sp, c, 1, stream));
-    HGX_TRY(stage_col(st_op32, op, c, 1, stream));
-    HGX_TRY(stage_col(st_ts, ts, c, 1, stream));
-    HGX_TRY(stage_col(st_coin, coin, c, 1, stream));
-    HGX_TRY(stage_col(st_S, S, c, 32, stream));
-    HGX_TRY(stage_col(st_ntx, ntx, c, 1, stream));
-    in.creator = st_creator.p; in.index32 = st_index32.p; in.sp32 = st_sp32.p; in.op32 = st_op32.p;
-    in.ts = st_ts.p; in.coin = st_coin.p; in.S = st_S.p; in.ntx = st_ntx.p;
-    if (count > 0) ids_known = false;
+    // a copy per column: the structure in the table's order, the payload (behind the decode) in the
+    // order of a batch staged whole, S into the staging with the rest
+    auto copy_cols = [&](bool payload) {
+        for (int k = 0; k < fs.n; k++) {
+            const ColSpec& cs = fs.col[payload ? fs.whole[k] : k];
+            if (is_payload(cs) != payload) continue;
+            const size_t bytes = col_bytes(cs, count, hc.n_exc);
+            HGX_TRY(stage_buf(cs.id, bytes, p));
+            at[cs.id] = p;
+            if (bytes || cs.kind != kColException)
+                HGX_TRY(hipMemcpyAsync(p, hc.col[cs.id], bytes, hipMemcpyHostToDevice, stream));
+        }
+        return hipSuccess;
+    };
+    if (one_copy) {
+        size_t off[kMaxFormCols];
+        HGX_TRY(stage_pinned(hc, count, off));
+        for (int i = 0; i < fs.n; i++) at[fs.col[i].id] = st_pack.p + off[i];
+    } else {
+        HGX_TRY(copy_cols(false));
+    }
+    if (packed) {
+        launch_unpack_packed(stream, count, E, (const uint16_t*)at[kColCreator16], (const uint16_t*)at[kColSpBack],
+                             (const uint16_t*)at[kColOpBack], hc.n_exc, (const int64_t*)at[kColExcPos],
+                             (const int32_t*)at[kColExcSp], (const int32_t*)at[kColExcOp], st_creator.p, st_sp32.p,
+                             st_op32.p);
+        HGX_TRY(hipGetLastError());
+        at[kColCreator] = st_creator.p; at[kColSp32] = st_sp32.p; at[kColOp32] = st_op32.p;
+    }
+    if (part == kStageAll && !one_copy) HGX_TRY(copy_cols(true));
+    for (int id = 0; id < kNumCols; id++)
+        if (at[id]) set_col(in, (ColId)id, at[id]);
+    // (an insert of compact columns brings the coin byte, not the event's id)
+    if (part == kStageAll && hc.form != Form::wide && count > 0) ids_known = false;
     return hipSuccess;
 }
 
@@ -610,158 +641,70 @@ hipError_t Engine::insert(const InsertIn& in, int64_t count, InsertOut& out) {
     return insert_impl(in, count, out, nullptr);
 }
 
-hipError_t Engine::insert_split_begin(const int32_t* creator, const int64_t* index, const int64_t* sp,
-                                      const int64_t* op, int64_t count, InsertOut& out) {
-    const size_t c = (size_t)count;
-    HGX_TRY(stage_col(st_creator, creator, c, 1, stream));
-    HGX_TRY(stage_col(st_index, index, c, 1, stream));
-    HGX_TRY(stage_col(st_sp, sp, c, 1, stream));
-    HGX_TRY(stage_col(st_op, op, c, 1, stream));
-    InsertIn in{};
-    in.creator = st_creator.p; in.index = st_index.p; in.sp = st_sp.p; in.op = st_op.p;   // no payload yet
-    split32 = false;
-    return insert_impl(in, count, out, nullptr, kCommitStructure);
-}
-
-hipError_t Engine::insert_split_begin32(const int32_t* creator, const int32_t* index, const int32_t* sp,
-                                        const int32_t* op, int64_t count, InsertOut& out) {
-    const size_t c = (size_t)count;
-    HGX_TRY(stage_col(st_creator, creator, c, 1, stream));
-    HGX_TRY(stage_col(st_index32, index, c, 1, stream));
-    HGX_TRY(stage_col(st_sp32, sp, c, 1, stream));
-    HGX_TRY(stage_col(st_op32, op, c, 1, stream));
-    InsertIn in{};
-    in.creator = st_creator.p; in.index32 = st_index32.p; in.sp32 = st_sp32.p; in.op32 = st_op32.p;
-    split32 = true;
-    return insert_impl(in, count, out, nullptr, kCommitStructure);
-}
-
-hipError_t Engine::stage_packed(const Packed& pk, int64_t count, InsertIn& in, const int64_t* ts, const uint8_t* coin,
-                                const uint8_t* S, const int32_t* ntx) {
-    const size_t c = (size_t)count, x = (size_t)pk.n_exc;
-    in = InsertIn{};
-    if (st_creator.n < c) HGX_TRY(st_creator.alloc(c));
-    if (st_sp32.n < c) HGX_TRY(st_sp32.alloc(c));
-    if (st_op32.n < c) HGX_TRY(st_op32.alloc(c));
-    if (ts && count <= kPackEvents) {   // a sync-sized batch: one pinned packed copy (as stage_host32)
-        const void* src[11] = {pk.creator, pk.index, pk.spb, pk.opb, ts, coin, S, ntx, pk.exc_pos, pk.exc_sp, pk.exc_op};
-        const size_t bytes[11] = {2 * c, 4 * c, 2 * c, 2 * c, 8 * c, c, 32 * c, 4 * c, 8 * x, 4 * x, 4 * x};
-        size_t off[11];
-        HGX_TRY(stage_pinned(11, src, bytes, off));
-        uint8_t* d = st_pack.p;
-        launch_unpack_packed(stream, count, E, (const uint16_t*)(d + off[0]), (const uint16_t*)(d + off[2]),
-                             (const uint16_t*)(d + off[3]), pk.n_exc, (const int64_t*)(d + off[8]),
-                             (const int32_t*)(d + off[9]), (const int32_t*)(d + off[10]), st_creator.p, st_sp32.p,
-                             st_op32.p);
-        HGX_TRY(hipGetLastError());
-        in.creator = st_creator.p; in.index32 = (const int32_t*)(d + off[1]); in.sp32 = st_sp32.p;
-        in.op32 = st_op32.p; in.ts = (const int64_t*)(d + off[4]); in.coin = d + off[5]; in.S = d + off[6];
-        in.ntx = (const int32_t*)(d + off[7]);
-        if (count > 0) ids_known = false;
-        return hipSuccess;
-    }
-    HGX_TRY(stage_col(st_c16, pk.creator, c, 1, stream));
-    HGX_TRY(stage_col(st_index32, pk.index, c, 1, stream));
-    HGX_TRY(stage_col(st_spb, pk.spb, c, 1, stream));
-    HGX_TRY(stage_col(st_opb, pk.opb, c, 1, stream));
-    if (x) {
-        HGX_TRY(stage_col(st_exc_pos, pk.exc_pos, x, 1, stream));
-        HGX_TRY(stage_col(st_exc_sp, pk.exc_sp, x, 1, stream));
-        HGX_TRY(stage_col(st_exc_op, pk.exc_op, x, 1, stream));
-    }
-    launch_unpack_packed(stream, count, E, st_c16.p, st_spb.p, st_opb.p, pk.n_exc, st_exc_pos.p, st_exc_sp.p,
-                         st_exc_op.p, st_creator.p, st_sp32.p, st_op32.p);
-    HGX_TRY(hipGetLastError());
-    in.creator = st_creator.p; in.index32 = st_index32.p; in.sp32 = st_sp32.p; in.op32 = st_op32.p;
-    if (ts) {
-        HGX_TRY(stage_col(st_ts, ts, c, 1, stream));
-        HGX_TRY(stage_col(st_coin, coin, c, 1, stream));
-        HGX_TRY(stage_col(st_S, S, c, 32, stream));
-        HGX_TRY(stage_col(st_ntx, ntx, c, 1, stream));
-        in.ts = st_ts.p; in.coin = st_coin.p; in.S = st_S.p; in.ntx = st_ntx.p;
-        if (count > 0) ids_known = false;
-    }
-    return hipSuccess;
-}
-
-hipError_t Engine::insert_split_begin_packed(const Packed& pk, int64_t count, InsertOut& out) {
+hipError_t Engine::insert_split_begin(const HostCols& hc, int64_t count, InsertOut& out) {
     InsertIn in;
-    HGX_TRY(stage_packed(pk, count, in));   // (no payload yet)
-    split32 = true;
+    HGX_TRY(stage(hc, count, kStageStructure, in));   // (no payload yet)
+    flight = hc.form == Form::wide ? kFlightWide : kFlightCompact;
     return insert_impl(in, count, out, nullptr, kCommitStructure);
 }
 
-hipError_t Engine::payload_begin32(const int64_t* ts, const uint8_t* coin, const uint8_t* S, const int32_t* ntx,
-                                   int64_t m_ok) {
+hipError_t Engine::payload_streams() {
     if (!stream2) {
         HGX_TRY(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));
         HGX_TRY(hipEventCreateWithFlags(&ev_pay, hipEventDisableTiming));
     }
-    const size_t c = (size_t)m_ok;
-    if (st_ts.n < c) HGX_TRY(st_ts.alloc(c));
-    if (st_coin.n < c) HGX_TRY(st_coin.alloc(c));
-    if (st_ntx.n < c) HGX_TRY(st_ntx.alloc(c));
     if (!ev_pay_S) HGX_TRY(hipEventCreateWithFlags(&ev_pay_S, hipEventDisableTiming));
-    if (pay_thread.joinable()) pay_thread.join();
-    pay_err = hipSuccess;
-    pay32 = true;
-    pay_stage = 0;
-    pay_S_pending = true;
-    pay_commit_pending = true;
-    pay_E0 = E - m_ok;
-    pay_m = m_ok;
-    pay_host_ms = 0;
-    if (m_ok > 0) ids_known = false;
-    uint8_t* S_dst = g_S.p + 32 * (size_t)(E - m_ok);   // the accepted prefix (just appended): gids E - m_ok ..
-    pay_thread = std::thread([=]() {
-        hipError_t e = hipSetDevice(dev);
-        if (c && e == hipSuccess) e = hipMemcpyAsync(st_ts.p, ts, c * 8, hipMemcpyHostToDevice, stream2);
-        if (c && e == hipSuccess) e = hipMemcpyAsync(st_coin.p, coin, c, hipMemcpyHostToDevice, stream2);
-        if (c && e == hipSuccess) e = hipMemcpyAsync(st_ntx.p, ntx, c * 4, hipMemcpyHostToDevice, stream2);
-        if (e == hipSuccess) e = hipEventRecord(ev_pay, stream2);
-        pay_err_a = e;
-        pay_stage.store(1, std::memory_order_release);
-        if (c && e == hipSuccess) e = hipMemcpyAsync(S_dst, S, c * 32, hipMemcpyHostToDevice, stream2);
-        if (e == hipSuccess) e = hipEventRecord(ev_pay_S, stream2);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream2);
-        pay_err = e;
-    });
     return hipSuccess;
 }
 
-hipError_t Engine::payload_begin(const int64_t* ts, const uint8_t* hash, const uint8_t* S, const int32_t* ntx,
-                                 const int32_t* nil, int64_t m_ok) {
-    if (!stream2) {
-        HGX_TRY(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));
-        HGX_TRY(hipEventCreateWithFlags(&ev_pay, hipEventDisableTiming));
+// The payload columns of events [E0, E0 + c) on stream2: the first stage into the staging columns and
+// ev_pay (pay_stage = 1 releases payload_commit), then the late stage (S of the compact payload)
+// straight into the event store and ev_pay_S.
+hipError_t Engine::copy_payload(const HostCols& hc, size_t c, size_t E0, hipError_t e, const std::atomic<int>* stop) {
+    const FormSpec& fs = form_spec(hc.form);
+    auto go = [&]() { return c && e == hipSuccess && !(stop && stop->load(std::memory_order_acquire)); };
+    bool late = false;
+    void* p = nullptr;
+    for (int i = 0; i < fs.n; i++) {
+        const ColSpec& cs = fs.col[i];
+        late |= cs.kind == kColPayloadLate;
+        if (cs.kind != kColPayload || !go()) continue;
+        e = stage_buf(cs.id, 0, p);   // (sized by the caller)
+        if (e == hipSuccess) e = hipMemcpyAsync(p, hc.col[cs.id], c * cs.bytes, hipMemcpyHostToDevice, stream2);
     }
-    const size_t c = (size_t)m_ok;   // the accepted prefix only
-    if (st_ts.n < c) HGX_TRY(st_ts.alloc(c));
-    if (st_hash.n < 32 * c) HGX_TRY(st_hash.alloc(32 * c));
-    if (st_S.n < 32 * c) HGX_TRY(st_S.alloc(32 * c));
-    if (st_ntx.n < c) HGX_TRY(st_ntx.alloc(c));
-    if (st_nil.n < c) HGX_TRY(st_nil.alloc(c));
+    if (e == hipSuccess) e = hipEventRecord(ev_pay, stream2);
+    pay_err_a = e;
+    pay_stage.store(1, std::memory_order_release);
+    if (late) {
+        if (go()) e = hipMemcpyAsync(g_S.p + 32 * E0, hc.col[kColS], c * 32, hipMemcpyHostToDevice, stream2);
+        if (e == hipSuccess) e = hipEventRecord(ev_pay_S, stream2);
+    }
+    const hipError_t es = hipStreamSynchronize(stream2);   // the caller's buffers are read completely
+    return e != hipSuccess ? e : es;
+}
+
+hipError_t Engine::payload_begin(const HostCols& hc, int64_t m_ok) {
+    HGX_TRY(payload_streams());
+    const FormSpec& fs = form_spec(hc.form);
+    const size_t c = (size_t)m_ok;   // the accepted prefix only (just appended): gids E - m_ok ..
+    bool late = false;
+    void* p = nullptr;
+    for (int i = 0; i < fs.n; i++) {
+        late |= fs.col[i].kind == kColPayloadLate;
+        if (fs.col[i].kind == kColPayload) HGX_TRY(stage_buf(fs.col[i].id, c * fs.col[i].bytes, p));
+    }
     if (pay_thread.joinable()) pay_thread.join();
     pay_err = hipSuccess;
-    pay32 = false;
-    pay_S_pending = false;
+    pay_stage = 0;
+    pay_S_pending = late;
     pay_commit_pending = true;
     pay_E0 = E - m_ok;
     pay_m = m_ok;
     pay_host_ms = 0;
+    if (hc.form != Form::wide && m_ok > 0) ids_known = false;
     // pageable host memory: each copy returns once its source has been consumed, so the copies
     // run on their own host thread (and stream) beside the DivideRounds launches
-    pay_thread = std::thread([=]() {
-        hipError_t e = hipSetDevice(dev);
-        if (c && e == hipSuccess) e = hipMemcpyAsync(st_ts.p, ts, c * 8, hipMemcpyHostToDevice, stream2);
-        if (c && e == hipSuccess) e = hipMemcpyAsync(st_hash.p, hash, c * 32, hipMemcpyHostToDevice, stream2);
-        if (c && e == hipSuccess) e = hipMemcpyAsync(st_S.p, S, c * 32, hipMemcpyHostToDevice, stream2);
-        if (c && e == hipSuccess) e = hipMemcpyAsync(st_ntx.p, ntx, c * 4, hipMemcpyHostToDevice, stream2);
-        if (c && e == hipSuccess) e = hipMemcpyAsync(st_nil.p, nil, c * 4, hipMemcpyHostToDevice, stream2);
-        if (e == hipSuccess) e = hipEventRecord(ev_pay, stream2);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream2);   // the caller's buffers are read completely
-        pay_err = e;
-    });
+    pay_thread = std::thread([this, hc, c, E0 = (size_t)pay_E0]() { pay_err = copy_payload(hc, c, E0, hipSetDevice(dev), nullptr); });
     return hipSuccess;
 }
 
@@ -787,13 +730,16 @@ hipError_t Engine::payload_commit(bool positions, hipStream_t on) {
         HGX_TRY(pay_err);
     }
     HGX_TRY(hipStreamWaitEvent(on, ev_pay, 0));
+    // the staging columns of the batch in flight (without the late S: it lands in the store itself)
     InsertIn in{};
-    in.creator = st_creator.p; in.ts = st_ts.p; in.S = pay_S_pending ? nullptr : st_S.p; in.ntx = st_ntx.p;
-    if (split32) { in.index32 = st_index32.p; in.sp32 = st_sp32.p; in.op32 = st_op32.p; }
-    else { in.index = st_index.p; in.sp = st_sp.p; in.op = st_op.p; }
-    if (pay32) in.coin = st_coin.p;
-    else { in.hash = st_hash.p; in.nil = st_nil.p; }
-    split32 = false;
+    const FormSpec& fs = form_spec(flight == kFlightWide ? Form::wide : Form::compact);
+    void* p = nullptr;
+    for (int i = 0; i < fs.n; i++)
+        if (fs.col[i].kind != kColPayloadLate) {
+            HGX_TRY(stage_buf(fs.col[i].id, 0, p));
+            set_col(in, fs.col[i].id, p);
+        }
+    flight = kFlightNone;
     launch_insert_commit(on, pay_m, nullptr, nullptr, pay_E0, n, in, insert_state(), kCommitPayload);
     // (the layout ran before the timestamps were committed)
     if (positions) launch_ts_to_pos(on, pay_E0, pay_m, g_pos.p, g_ts.p, p_ts.p);
@@ -845,10 +791,6 @@ hipError_t Engine::insert_impl(const InsertIn& in, int64_t count, InsertOut& out
         HGX_TRY(copy_to_pinned(h_small, ins_fail.p, 8, 0xFF));
         if (fail_sig) HGX_TRY(copy_to_pinned(h_small + 2, fail_sig, 8));
     }
-    out.last_gid.resize(C);
-    out.last_index.resize(C);
-    out.chain_base.resize(C);
-    out.graph_loaded.resize(G);
     // the first-failure words and the whole state block into pinned memory (one launch), then
     // the host mirrors
     HGX_TRY(copy_to_pinned(h_ins, ins_blk.p, ins_blk.n * sizeof(int32_t)));
@@ -878,11 +820,16 @@ hipError_t Engine::insert_impl(const InsertIn& in, int64_t count, InsertOut& out
         }
         E = E0 + m_ok;
     }
-    std::memcpy(out.last_gid.data(), h_ins, (size_t)C * 4);
-    std::memcpy(out.last_index.data(), h_ins + C, (size_t)C * 4);
-    std::memcpy(out.chain_base.data(), h_ins + 2 * C, (size_t)C * 4);
-    std::memcpy(out.graph_loaded.data(), h_ins + ins_gl_off, (size_t)G * 8);
+    read_insert_state(out);
     return hipSuccess;
+}
+
+void Engine::read_insert_state(InsertOut& out) const {
+    out.last_gid.assign(h_ins, h_ins + C);
+    out.last_index.assign(h_ins + C, h_ins + 2 * C);
+    out.chain_base.assign(h_ins + 2 * C, h_ins + 3 * C);
+    out.graph_loaded.resize(G);
+    std::memcpy(out.graph_loaded.data(), h_ins + ins_gl_off, (size_t)G * 8);
 }
 
 hipError_t Engine::clear() {
@@ -901,9 +848,7 @@ hipError_t Engine::clear() {
 }
 
 // ---- the pipelined ingest --------------------------------------------------
-hipError_t Engine::insert_pipe32(const int32_t* creator, const int32_t* index, const int32_t* sp, const int32_t* op,
-                                 const int64_t* ts, const uint8_t* coin, const uint8_t* S, const int32_t* ntx,
-                                 int64_t count, InsertOut& out, bool& taken) {
+hipError_t Engine::insert_pipe32(const HostCols& hc, int64_t count, InsertOut& out, bool& taken) {
     taken = false;
     pipe_used = 0;
     if (pipe_pieces <= 0 || count < pipe_min || count < 2 || count > cap || E != 0 || rooted || G != 1 || grp ||
@@ -930,20 +875,13 @@ hipError_t Engine::insert_pipe32(const int32_t* creator, const int32_t* index, c
         cut[k] = count * seg_cut[k] / nts;   // (k_la_wave's segment bounds)
     }
     const size_t c = (size_t)count, Cz = (size_t)C;
-    if (st_creator.n < c) HGX_TRY(st_creator.alloc(c));
-    if (st_index32.n < c) HGX_TRY(st_index32.alloc(c));
-    if (st_sp32.n < c) HGX_TRY(st_sp32.alloc(c));
-    if (st_op32.n < c) HGX_TRY(st_op32.alloc(c));
-    if (st_ts.n < c) HGX_TRY(st_ts.alloc(c));
-    if (st_coin.n < c) HGX_TRY(st_coin.alloc(c));
-    if (st_ntx.n < c) HGX_TRY(st_ntx.alloc(c));
+    const FormSpec& fs = form_spec(Form::compact);
+    void* p = nullptr;
+    for (int i = 0; i < fs.n; i++)   // (S goes straight into g_S)
+        if (fs.col[i].kind != kColPayloadLate) HGX_TRY(stage_buf(fs.col[i].id, c * fs.col[i].bytes, p));
     const size_t o_hist = 64, o_lim = o_hist + kPipeMaxPieces * Cz;
     if (pipe_buf.n < o_lim + kPipeMaxPieces * Cz) HGX_TRY(pipe_buf.alloc(o_lim + kPipeMaxPieces * Cz));
-    if (!stream2) {
-        HGX_TRY(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));
-        HGX_TRY(hipEventCreateWithFlags(&ev_pay, hipEventDisableTiming));
-    }
-    if (!ev_pay_S) HGX_TRY(hipEventCreateWithFlags(&ev_pay_S, hipEventDisableTiming));
+    HGX_TRY(payload_streams());
     if (!stream_o) {
         HGX_TRY(hipStreamCreateWithFlags(&stream_o, hipStreamNonBlocking));
         for (int k = 0; k <= kOrderParts; k++) HGX_TRY(hipEventCreateWithFlags(&ev_o[k], hipEventDisableTiming));
@@ -964,11 +902,12 @@ hipError_t Engine::insert_pipe32(const int32_t* creator, const int32_t* index, c
     pay_stage = 0;
     // one copier: the creator column, then index / sp / op piece by piece, an event behind each
     // (a host thread: a copy from pageable memory returns only once its source has been consumed),
-    // then the payload as payload_begin32's copier: ts / coin / ntx and ev_pay, S into g_S (the
-    // context is empty: gid 0) and ev_pay_S. pipe_stop (a way out of the pipeline) ends it at the
-    // next column; what it wrote by then the serial path's own payload copy overwrites.
+    // then the payload as payload_begin's copier (copy_payload; the context is empty: S at gid 0).
+    // pipe_stop (a way out of the pipeline) ends it at the next column; what it wrote by then the
+    // serial path's own payload copy overwrites.
     std::vector<int64_t> cuts(cut, cut + pieces + 1);
-    uint8_t* S_dst = g_S.p;
+    const int32_t *creator = (const int32_t*)hc.col[kColCreator], *index = (const int32_t*)hc.col[kColIndex32],
+                  *sp = (const int32_t*)hc.col[kColSp32], *op = (const int32_t*)hc.col[kColOp32];
     pipe_thread = std::thread([=]() {
         hipError_t e = hipSetDevice(dev);
         if (e == hipSuccess) e = hipMemcpyAsync(st_creator.p, creator, c * 4, hipMemcpyHostToDevice, stream2);
@@ -985,19 +924,9 @@ hipError_t Engine::insert_pipe32(const int32_t* creator, const int32_t* index, c
             if (e != hipSuccess) pipe_err = e;
             pipe_stage.store(k + 2, std::memory_order_release);
         }
-        auto go = [&]() { return e == hipSuccess && !pipe_stop.load(std::memory_order_acquire); };
-        hipError_t ep = e;   // the payload's copies (pay_err_a / pay_err, read once the pipeline was taken)
-        if (go()) ep = hipMemcpyAsync(st_ts.p, ts, c * 8, hipMemcpyHostToDevice, stream2);
-        if (ep == hipSuccess && go()) ep = hipMemcpyAsync(st_coin.p, coin, c, hipMemcpyHostToDevice, stream2);
-        if (ep == hipSuccess && go()) ep = hipMemcpyAsync(st_ntx.p, ntx, c * 4, hipMemcpyHostToDevice, stream2);
-        if (ep == hipSuccess) ep = hipEventRecord(ev_pay, stream2);
-        pay_err_a = ep;
-        pay_stage.store(1, std::memory_order_release);
-        if (ep == hipSuccess && go()) ep = hipMemcpyAsync(S_dst, S, c * 32, hipMemcpyHostToDevice, stream2);
-        if (ep == hipSuccess) ep = hipEventRecord(ev_pay_S, stream2);
-        const hipError_t es = hipStreamSynchronize(stream2);   // the caller's columns are read completely
-        if (e == hipSuccess && es != hipSuccess) pipe_err = es;
-        pay_err = ep != hipSuccess ? ep : es;
+        // (pay_err_a / pay_err are read once the pipeline was taken)
+        pay_err = copy_payload(hc, c, 0, e, &pipe_stop);
+        if (e == hipSuccess && pay_err != hipSuccess) pipe_err = pay_err;
     });
     // every way out joins the copier; `fail` leaves the context empty for the serial path
     auto stop = [&](hipError_t e) {
@@ -1093,9 +1022,9 @@ hipError_t Engine::insert_pipe32(const int32_t* creator, const int32_t* index, c
         E = count;
         return clear();
     }
-    // the copier runs on as the payload's: payload_commit and payload_wait_S find it as payload_begin32's
+    // the copier runs on as the payload's: payload_commit and payload_wait_S find it as payload_begin's
     pay_thread = std::move(pipe_thread);
-    pay32 = true;
+    flight = kFlightCompact;
     pay_S_pending = true;
     pay_commit_pending = true;
     pay_E0 = 0;
@@ -1103,17 +1032,9 @@ hipError_t Engine::insert_pipe32(const int32_t* creator, const int32_t* index, c
     pay_host_ms = 0;
     ids_known = false;
     E = count;
-    split32 = true;
     out = InsertOut();
     out.accepted = count;
-    out.last_gid.resize(C);
-    out.last_index.resize(C);
-    out.chain_base.resize(C);
-    out.graph_loaded.resize(G);
-    std::memcpy(out.last_gid.data(), h_ins, Cz * 4);
-    std::memcpy(out.last_index.data(), h_ins + C, Cz * 4);
-    std::memcpy(out.chain_base.data(), h_ins + 2 * C, Cz * 4);
-    std::memcpy(out.graph_loaded.data(), h_ins + ins_gl_off, (size_t)G * 8);
+    read_insert_state(out);
     pipe_ready = true;
     pipe_En = count;
     pipe_nts = nts;

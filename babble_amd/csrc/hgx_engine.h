@@ -12,6 +12,7 @@
 #include <thread>
 #include <vector>
 
+#include "hgx_ingest_cols.h"
 #include "hgx_kernels.h"
 
 namespace hgx {
@@ -171,20 +172,21 @@ class Engine {
     // participants' public keys (65 bytes each, C of them): device window tables built once
     hipError_t set_keys(const uint8_t* keys65);
     bool keys_set = false;
-    hipError_t stage_host(const int32_t* creator, const int64_t* index, const int64_t* sp, const int64_t* op,
-                          const int64_t* ts, const uint8_t* hash, const uint8_t* S, const int32_t* ntx,
-                          const int32_t* nil, int64_t count, InsertIn& in);
+    // A batch's host columns (hgx_ingest_cols.h, any form) staged to HBM and `in` pointed at them:
+    // kStageAll every column (a batch of at most kPackEvents in one pinned copy, else a copy per
+    // column), kStageStructure the structure columns alone. The packed form's structure is decoded
+    // into the compact staging columns (launch_unpack_packed); its exceptions are already checked.
+    enum StagePart { kStageStructure, kStageAll };
+    hipError_t stage(const HostCols& hc, int64_t count, StagePart part, InsertIn& in);
     // hgx_insert_and_run's split insert of host columns: the structure columns (creator, index,
     // parents) are staged, validated and committed now (out.graph_loaded is not final); a worker
-    // thread copies the payload columns (timestamps, hash, S, transactions) of the accepted
+    // thread copies the payload columns (timestamps, hash or coin, S, transactions) of the accepted
     // prefix on a second stream while the caller runs DivideRounds; payload_commit / payload_finish
     // (below) join it, commit the payload, rewrite the layout's timestamps and the candidates' coins,
     // and payload_loaded returns the graphs' loaded counts. Not for rooted contexts (Root.Others needs
     // the hash at validation).
-    hipError_t insert_split_begin(const int32_t* creator, const int64_t* index, const int64_t* sp, const int64_t* op,
-                                  int64_t count, InsertOut& out);
-    hipError_t payload_begin(const int64_t* ts, const uint8_t* hash, const uint8_t* S, const int32_t* ntx,
-                             const int32_t* nil, int64_t m_ok);
+    hipError_t insert_split_begin(const HostCols& hc, int64_t count, InsertOut& out);
+    hipError_t payload_begin(const HostCols& hc, int64_t m_ok);
     // payload_end in three parts, so that no host wait stands between the rounds and DecideFame:
     // payload_commit waits for the first columns, commits them and (positions) rewrites the layout's
     // timestamps -- divide_rounds queues it for the compact payload ahead of k_fd_build, where the
@@ -199,31 +201,6 @@ class Engine {
     // the compact payload's S column (copied last, straight into g_S): wait for it (the sort's
     // tie-break, a read-back, a clear) and for the caller's buffer to be read completely
     hipError_t payload_wait_S();
-    // the same three for the compact columns of hgx_events32 (int32 Index and parents, the coin
-    // byte instead of the event id, len(Transactions) with -1 for nil): 61 instead of 108 bytes
-    // per event cross PCIe
-    hipError_t stage_host32(const int32_t* creator, const int32_t* index, const int32_t* sp, const int32_t* op,
-                            const int64_t* ts, const uint8_t* coin, const uint8_t* S, const int32_t* ntx, int64_t count,
-                            InsertIn& in);
-    hipError_t insert_split_begin32(const int32_t* creator, const int32_t* index, const int32_t* sp, const int32_t* op,
-                                    int64_t count, InsertOut& out);
-    hipError_t payload_begin32(const int64_t* ts, const uint8_t* coin, const uint8_t* S, const int32_t* ntx, int64_t m_ok);
-    // hgx_events_packed's structure columns (10 bytes per event) copied to HBM and decoded into
-    // the hgx_events32 staging columns (launch_unpack_packed); exceptions already checked
-    struct Packed {
-        const uint16_t* creator;
-        const int32_t* index;
-        const uint16_t* spb;
-        const uint16_t* opb;
-        int64_t n_exc;
-        const int64_t* exc_pos;
-        const int32_t* exc_sp;
-        const int32_t* exc_op;
-    };
-    // (with the payload columns when ts is not null: hgx_insert_events_packed)
-    hipError_t stage_packed(const Packed& pk, int64_t count, InsertIn& in, const int64_t* ts = nullptr,
-                            const uint8_t* coin = nullptr, const uint8_t* S = nullptr, const int32_t* ntx = nullptr);
-    hipError_t insert_split_begin_packed(const Packed& pk, int64_t count, InsertOut& out);
     // forget every event (a fresh NewHashgraph); allocations are kept
     hipError_t clear();
     // hgx_prune_to_frame (hgx_compact.hip) in two steps. prune_stage changes nothing
@@ -277,14 +254,12 @@ class Engine {
     // follow in pieces cut at time-segment boundaries, and each piece is inserted, laid out and its
     // segments' lastAncestors main pass launched while the later pieces still cross PCIe. taken =
     // false: nothing was inserted (the path does not apply, or a check failed and the context was
-    // cleared) and the caller runs insert_split_begin32 on the same columns.
-    // The copier goes on with the payload columns right behind the last piece (ts, coin, ntx into the
-    // staging columns, S straight into g_S at gid 0), so PCIe does not idle while the call finishes;
-    // taken = true leaves the payload in flight exactly as payload_begin32 would. taken = false: the
-    // copier has been joined, and whatever it wrote early is overwritten by the caller's payload_begin32.
-    hipError_t insert_pipe32(const int32_t* creator, const int32_t* index, const int32_t* sp, const int32_t* op,
-                             const int64_t* ts, const uint8_t* coin, const uint8_t* S, const int32_t* ntx,
-                             int64_t count, InsertOut& out, bool& taken);
+    // cleared) and the caller runs insert_split_begin on the same columns.
+    // The copier goes on with the payload columns right behind the last piece (copy_payload: ts, coin,
+    // ntx into the staging columns, S straight into g_S at gid 0), so PCIe does not idle while the call
+    // finishes; taken = true leaves the payload in flight as payload_begin would. taken = false: the
+    // copier has been joined, and whatever it wrote early is overwritten by the caller's payload_begin.
+    hipError_t insert_pipe32(const HostCols& hc, int64_t count, InsertOut& out, bool& taken);
     static constexpr int kPipeSegMult = 2;   // time segments of a pipelined ingest over a serial rebuild's
     int pipe_pieces = 4;                // hgx_set_ingest_pipeline: 0 = always the serial path
     int64_t pipe_min = 4000000;         // ... batches of at least this many events
@@ -412,8 +387,15 @@ class Engine {
     bool pipe_ready = false;          // layout and main pass done for pipe_En / pipe_nts / pipe_off / pipe_compact
     int64_t pipe_En = 0;
     int pipe_nts = 0, pipe_compact = 0;
-    bool pay32 = false;              // the payload in flight is hgx_events32's (coin byte, ntx -1 = nil)
-    bool split32 = false;            // the structure columns staged by insert_split_begin32
+    // the form of the split batch in flight, set with its structure (a packed batch is compact once
+    // decoded); payload_commit reads the staging columns it names
+    enum Flight { kFlightNone, kFlightWide, kFlightCompact } flight = kFlightNone;
+    hipError_t payload_streams();    // stream2, ev_pay and ev_pay_S, created on first use
+    // the payload copier's body, on the copier's thread behind its hipSetDevice (e: that thread's
+    // error so far; stop: a flag that ends it at the next column, or null)
+    hipError_t copy_payload(const HostCols& hc, size_t c, size_t E0, hipError_t e, const std::atomic<int>* stop);
+    hipError_t stage_buf(ColId id, size_t bytes, void*& p);   // the column's staging buffer, of at least `bytes`
+    void read_insert_state(InsertOut& out) const;             // h_ins, once the stream has been synchronized
     hipEvent_t ev_pay = nullptr;
     // the S column is copied last, straight into g_S: only FindOrder's sort reads it, so DecideFame
     // and the first FindOrder kernels run while it crosses PCIe (payload_wait_S before the sort)
@@ -485,7 +467,7 @@ class Engine {
     // batches of at most kPackEvents from host memory: the columns packed in one pinned buffer,
     // one H2D copy into st_pack
     static constexpr int64_t kPackEvents = 65536;
-    hipError_t stage_pinned(int k, const void* const* src, const size_t* bytes, size_t* off);
+    hipError_t stage_pinned(const HostCols& hc, int64_t count, size_t* off);
     DBuf<uint8_t> st_pack;
     uint8_t* h_pack = nullptr;
     size_t h_pack_cap = 0;

@@ -239,21 +239,41 @@ class Hashgraph:
             pass
 
     # ------------------------------------------------------------------ inserts
-    def insert_arrays(self, creator, index, sp, op, ts, hash32, s32, ntx, txnil) -> int:
-        """Bulk InsertEvent(e, true) in order; raises HgxError on the first rejected event."""
-        a = dict(creator=np.ascontiguousarray(creator, np.int32), index=np.ascontiguousarray(index, np.int64),
-                 sp=np.ascontiguousarray(sp, np.int64), op=np.ascontiguousarray(op, np.int64),
-                 ts=np.ascontiguousarray(ts, np.int64), h=np.ascontiguousarray(hash32, np.uint8),
-                 s=np.ascontiguousarray(s32, np.uint8), ntx=np.ascontiguousarray(ntx, np.int32),
-                 nil=np.ascontiguousarray(txnil, np.int32))
-        cnt = int(a["creator"].shape[0])
-        ev = hgx_events(ptr(a["creator"]), ptr(a["index"]), ptr(a["sp"]), ptr(a["op"]), ptr(a["ts"]),
-                        ptr(a["h"]), ptr(a["s"]), ptr(a["ntx"]), ptr(a["nil"]))
+    def _insert_call(self, fn, *args) -> int:
+        """fn(ctx, *args, &n_inserted, &err): returns n_inserted; raises HgxError with .inserted = the
+        events inserted before the first rejected one, or the error a commit callback raised inside the
+        call."""
         err = hgx_error()
         n_ins = C.c_int64(0)
-        rc = self.L.hgx_insert_events(self.ctx, C.byref(ev), cnt, C.byref(n_ins), C.byref(err))
-        _lib.check(rc, err)
+        self._cb_error = None
+        rc = fn(self.ctx, *args, C.byref(n_ins), C.byref(err))
+        if rc:
+            e = HgxError(int(err.code or rc), err.msg.decode(errors="replace"))
+            e.inserted = n_ins.value
+            raise e
+        cb_err, self._cb_error = getattr(self, "_cb_error", None), None
+        if cb_err is not None:
+            raise cb_err
         return n_ins.value
+
+    @staticmethod
+    def _events_of(creator, index, sp, op, ts, hash32, s32, ntx, txnil):
+        """The hgx_events struct over contiguous copies of the columns (returned first: they must outlive it)."""
+        a = [np.ascontiguousarray(creator, np.int32), np.ascontiguousarray(index, np.int64),
+             np.ascontiguousarray(sp, np.int64), np.ascontiguousarray(op, np.int64), np.ascontiguousarray(ts, np.int64),
+             np.ascontiguousarray(hash32, np.uint8), np.ascontiguousarray(s32, np.uint8),
+             np.ascontiguousarray(ntx, np.int32), np.ascontiguousarray(txnil, np.int32)]
+        return a, hgx_events(*[ptr(x) for x in a])
+
+    def _trace_events(self, t, lo: int, hi: int):
+        sl = slice(lo, hi)
+        return self._events_of(t.creator[sl], t.index[sl], t.sp[sl], t.op[sl], t.ts[sl], t.hash[sl], t.s[sl], t.ntx[sl],
+                               t.txnil[sl])
+
+    def insert_arrays(self, creator, index, sp, op, ts, hash32, s32, ntx, txnil) -> int:
+        """Bulk InsertEvent(e, true) in order; raises HgxError on the first rejected event."""
+        a, ev = self._events_of(creator, index, sp, op, ts, hash32, s32, ntx, txnil)
+        return self._insert_call(self.L.hgx_insert_events, C.byref(ev), int(a[0].shape[0]))
 
     def set_participant_keys(self, keys65):
         """Participants' public keys (C x 65 bytes, participant id order) for Event.Verify."""
@@ -265,25 +285,10 @@ class Hashgraph:
         their body digests and signature R (S = the trace's S column). Raises HgxError on the first
         rejected event, with .inserted = events inserted before it."""
         hi = t.E if hi is None else hi
-        sl = slice(lo, hi)
-        a = dict(creator=np.ascontiguousarray(t.creator[sl], np.int32), index=np.ascontiguousarray(t.index[sl], np.int64),
-                 sp=np.ascontiguousarray(t.sp[sl], np.int64), op=np.ascontiguousarray(t.op[sl], np.int64),
-                 ts=np.ascontiguousarray(t.ts[sl], np.int64), h=np.ascontiguousarray(t.hash[sl], np.uint8),
-                 s=np.ascontiguousarray(t.s[sl], np.uint8), ntx=np.ascontiguousarray(t.ntx[sl], np.int32),
-                 nil=np.ascontiguousarray(t.txnil[sl], np.int32),
-                 d=np.ascontiguousarray(np.asarray(digest32)[sl], np.uint8),
-                 r=np.ascontiguousarray(np.asarray(r32)[sl], np.uint8))
-        ev = hgx_events(ptr(a["creator"]), ptr(a["index"]), ptr(a["sp"]), ptr(a["op"]), ptr(a["ts"]),
-                        ptr(a["h"]), ptr(a["s"]), ptr(a["ntx"]), ptr(a["nil"]))
-        err = hgx_error()
-        n_ins = C.c_int64(0)
-        rc = self.L.hgx_insert_events_verified(self.ctx, C.byref(ev), ptr(a["d"]), ptr(a["r"]), hi - lo,
-                                               C.byref(n_ins), C.byref(err))
-        if rc:
-            e = HgxError(int(err.code or rc), err.msg.decode(errors="replace"))
-            e.inserted = n_ins.value
-            raise e
-        return n_ins.value
+        a, ev = self._trace_events(t, lo, hi)
+        d = np.ascontiguousarray(np.asarray(digest32)[lo:hi], np.uint8)
+        r = np.ascontiguousarray(np.asarray(r32)[lo:hi], np.uint8)
+        return self._insert_call(self.L.hgx_insert_events_verified, C.byref(ev), ptr(d), ptr(r), hi - lo)
 
     def insert_bodies(self, cols: dict, lo: int = 0, hi: Optional[int] = None, other_parent_ids=None) -> np.ndarray:
         """InsertEvent with Event.Hash and Event.Verify computed on the device from the events' fields
@@ -294,36 +299,24 @@ class Hashgraph:
         hi = len(cols["creator"]) if hi is None else hi
         a, ev = _event_bodies_of(cols, lo, hi)
         ids = np.zeros((hi - lo, 32), np.uint8)
-        err = hgx_error()
-        n_ins = C.c_int64(0)
-        if other_parent_ids is None:
-            rc = self.L.hgx_insert_event_bodies(self.ctx, C.byref(ev), hi - lo, ptr(ids), C.byref(n_ins), C.byref(err))
-        else:
-            opi = np.ascontiguousarray(np.asarray(other_parent_ids, np.uint8).reshape(-1, 32)[lo:hi])
-            assert opi.shape[0] == hi - lo
-            rc = self.L.hgx_insert_event_bodies_ext(self.ctx, C.byref(ev), ptr(opi), hi - lo, ptr(ids), C.byref(n_ins),
-                                                    C.byref(err))
-        if rc:
-            e = HgxError(int(err.code or rc), err.msg.decode(errors="replace"))
-            e.inserted = n_ins.value
-            e.ids = ids[:n_ins.value]
-            raise e
+        try:
+            if other_parent_ids is None:
+                self._insert_call(self.L.hgx_insert_event_bodies, C.byref(ev), hi - lo, ptr(ids))
+            else:
+                opi = np.ascontiguousarray(np.asarray(other_parent_ids, np.uint8).reshape(-1, 32)[lo:hi])
+                assert opi.shape[0] == hi - lo
+                self._insert_call(self.L.hgx_insert_event_bodies_ext, C.byref(ev), ptr(opi), hi - lo, ptr(ids))
+        except HgxError as e:
+            e.ids = ids[:e.inserted]
+            raise
         return ids
 
     def insert_verified_device(self, dt: "DeviceTrace", d_digest, d_r, lo: int = 0, hi: Optional[int] = None) -> int:
         """The same with every column resident in HBM (d_digest / d_r: device addresses of 32-byte rows)."""
         hi = dt.E if hi is None else hi
         ev = dt.events(lo, hi)
-        err = hgx_error()
-        n_ins = C.c_int64(0)
-        rc = self.L.hgx_insert_events_verified_device(self.ctx, C.byref(ev), C.c_void_p(int(d_digest) + 32 * lo),
-                                                      C.c_void_p(int(d_r) + 32 * lo), hi - lo, C.byref(n_ins),
-                                                      C.byref(err))
-        if rc:
-            e = HgxError(int(err.code or rc), err.msg.decode(errors="replace"))
-            e.inserted = n_ins.value
-            raise e
-        return n_ins.value
+        return self._insert_call(self.L.hgx_insert_events_verified_device, C.byref(ev),
+                                 C.c_void_p(int(d_digest) + 32 * lo), C.c_void_p(int(d_r) + 32 * lo), hi - lo)
 
     def insert_wire(self, creator_id, index, sp_index, op_creator, op_index, ts, hash32, s32, ntx, txnil) -> int:
         """Core.Sync's loop over WireEvents (hgx_insert_wire_events): ReadWireInfo + InsertEvent(e, false)
@@ -334,14 +327,7 @@ class Hashgraph:
              np.ascontiguousarray(hash32, np.uint8), np.ascontiguousarray(s32, np.uint8),
              np.ascontiguousarray(ntx, np.int32), np.ascontiguousarray(txnil, np.int32)]
         ev = _lib.hgx_wire_events(*[ptr(x) for x in a])
-        err = hgx_error()
-        n_ins = C.c_int64(0)
-        rc = self.L.hgx_insert_wire_events(self.ctx, C.byref(ev), int(a[0].shape[0]), C.byref(n_ins), C.byref(err))
-        if rc:
-            e = HgxError(rc, err.msg.decode(errors="replace"))
-            e.inserted = n_ins.value
-            raise e
-        return n_ins.value
+        return self._insert_call(self.L.hgx_insert_wire_events, C.byref(ev), int(a[0].shape[0]))
 
     def insert_wire_bodies(self, cols: dict, lo: int = 0, hi: Optional[int] = None):
         """Core.Sync's loop over WireEvents from their wire fields alone (hgx_insert_wire_bodies): events
@@ -354,26 +340,18 @@ class Hashgraph:
         ids = np.zeros((hi - lo, 32), np.uint8)
         sp = np.full(hi - lo, -1, np.int64)
         op = np.full(hi - lo, -1, np.int64)
-        err = hgx_error()
-        n_ins = C.c_int64(0)
-        rc = self.L.hgx_insert_wire_bodies(self.ctx, C.byref(ev), hi - lo, ptr(ids), ptr(sp), ptr(op), C.byref(n_ins),
-                                           C.byref(err))
-        if rc:
-            e = HgxError(int(err.code or rc), err.msg.decode(errors="replace"))
-            e.inserted = n_ins.value
-            e.ids, e.self_parent, e.other_parent = ids[:n_ins.value], sp[:n_ins.value], op[:n_ins.value]
-            raise e
+        try:
+            self._insert_call(self.L.hgx_insert_wire_bodies, C.byref(ev), hi - lo, ptr(ids), ptr(sp), ptr(op))
+        except HgxError as e:
+            e.ids, e.self_parent, e.other_parent = ids[:e.inserted], sp[:e.inserted], op[:e.inserted]
+            raise
         return ids, sp, op
 
     def insert_device(self, dt: "DeviceTrace", lo: int = 0, hi: Optional[int] = None) -> int:
         """Bulk InsertEvent of a trace already resident in HBM (hgx_insert_events_device)."""
         hi = dt.E if hi is None else hi
         ev = dt.events(lo, hi)
-        err = hgx_error()
-        n_ins = C.c_int64(0)
-        rc = self.L.hgx_insert_events_device(self.ctx, C.byref(ev), hi - lo, C.byref(n_ins), C.byref(err))
-        _lib.check(rc, err)
-        return n_ins.value
+        return self._insert_call(self.L.hgx_insert_events_device, C.byref(ev), hi - lo)
 
     def clear(self):
         """Forget every event: a fresh NewHashgraph (device allocations kept)."""
@@ -392,26 +370,8 @@ class Hashgraph:
         trace inserted, then DivideRounds / DecideFame / FindOrder, the payload columns copied to HBM
         while DivideRounds runs. Raises HgxError like insert_trace (.inserted = the accepted prefix)."""
         hi = t.E if hi is None else hi
-        sl = slice(lo, hi)
-        a = dict(creator=np.ascontiguousarray(t.creator[sl], np.int32), index=np.ascontiguousarray(t.index[sl], np.int64),
-                 sp=np.ascontiguousarray(t.sp[sl], np.int64), op=np.ascontiguousarray(t.op[sl], np.int64),
-                 ts=np.ascontiguousarray(t.ts[sl], np.int64), h=np.ascontiguousarray(t.hash[sl], np.uint8),
-                 s=np.ascontiguousarray(t.s[sl], np.uint8), ntx=np.ascontiguousarray(t.ntx[sl], np.int32),
-                 nil=np.ascontiguousarray(t.txnil[sl], np.int32))
-        ev = hgx_events(ptr(a["creator"]), ptr(a["index"]), ptr(a["sp"]), ptr(a["op"]), ptr(a["ts"]),
-                        ptr(a["h"]), ptr(a["s"]), ptr(a["ntx"]), ptr(a["nil"]))
-        err = hgx_error()
-        n_ins = C.c_int64(0)
-        self._cb_error = None
-        rc = self.L.hgx_insert_and_run(self.ctx, C.byref(ev), hi - lo, C.byref(n_ins), C.byref(err))
-        if rc:
-            e = HgxError(int(err.code or rc), err.msg.decode(errors="replace"))
-            e.inserted = n_ins.value
-            raise e
-        cb_err, self._cb_error = getattr(self, "_cb_error", None), None
-        if cb_err is not None:
-            raise cb_err
-        return n_ins.value
+        a, ev = self._trace_events(t, lo, hi)
+        return self._insert_call(self.L.hgx_insert_and_run, C.byref(ev), hi - lo)
 
     def _events32(self, cols: dict, lo: int, hi: int):
         return _events32_of(cols, lo, hi)
@@ -420,49 +380,20 @@ class Hashgraph:
         """InsertEvent from the compact columns of compact_columns() (hgx_insert_events32)."""
         hi = len(cols["creator"]) if hi is None else hi
         a, ev = self._events32(cols, lo, hi)
-        err = hgx_error()
-        n_ins = C.c_int64(0)
-        rc = self.L.hgx_insert_events32(self.ctx, C.byref(ev), hi - lo, C.byref(n_ins), C.byref(err))
-        if rc:
-            e = HgxError(int(err.code or rc), err.msg.decode(errors="replace"))
-            e.inserted = n_ins.value
-            raise e
-        return n_ins.value
+        return self._insert_call(self.L.hgx_insert_events32, C.byref(ev), hi - lo)
 
     def insert_and_run32(self, cols: dict, lo: int = 0, hi: Optional[int] = None) -> int:
         """insert_and_run from the compact columns (hgx_insert_and_run32: 61 bytes per event)."""
         hi = len(cols["creator"]) if hi is None else hi
         a, ev = self._events32(cols, lo, hi)
-        err = hgx_error()
-        n_ins = C.c_int64(0)
-        self._cb_error = None
-        rc = self.L.hgx_insert_and_run32(self.ctx, C.byref(ev), hi - lo, C.byref(n_ins), C.byref(err))
-        if rc:
-            e = HgxError(int(err.code or rc), err.msg.decode(errors="replace"))
-            e.inserted = n_ins.value
-            raise e
-        cb_err, self._cb_error = getattr(self, "_cb_error", None), None
-        if cb_err is not None:
-            raise cb_err
-        return n_ins.value
+        return self._insert_call(self.L.hgx_insert_and_run32, C.byref(ev), hi - lo)
 
     def _packed_call(self, fn, pk: dict) -> int:
         m = len(pk["creator16"])
         ev = _lib.hgx_events_packed(ptr(pk["creator16"]), ptr(pk["index"]), ptr(pk["sp_back"]), ptr(pk["op_back"]),
                                     len(pk["exc_pos"]), ptr(pk["exc_pos"]), ptr(pk["exc_sp"]), ptr(pk["exc_op"]),
                                     ptr(pk["ts"]), ptr(pk["coin"]), ptr(pk["s"]), ptr(pk["ntx"]))
-        err = hgx_error()
-        n_ins = C.c_int64(0)
-        self._cb_error = None
-        rc = fn(self.ctx, C.byref(ev), m, C.byref(n_ins), C.byref(err))
-        if rc:
-            e = HgxError(int(err.code or rc), err.msg.decode(errors="replace"))
-            e.inserted = n_ins.value
-            raise e
-        cb_err, self._cb_error = getattr(self, "_cb_error", None), None
-        if cb_err is not None:
-            raise cb_err
-        return n_ins.value
+        return self._insert_call(fn, C.byref(ev), m)
 
     def insert_events_packed(self, pk: dict) -> int:
         """InsertEvent from pack_columns() output (hgx_insert_events_packed); its base must be

@@ -304,3 +304,49 @@ def test_packed_distance_before_the_first_event(back):
         b.insert_and_run32(cols)
     assert ei.value.inserted == k0 == ec.value.inserted and a.num_events() == k0
     assert ei.value.msg == ec.value.msg and ei.value.code == ec.value.code
+
+
+def test_packed_split_on_a_context_that_holds_events():
+    """hgx_insert_and_run_packed of 66 000 events (the split insert) on a context that already ran
+    consensus over 4 000: the late payload lands behind the resident events (S at gid 4 000 of the
+    store, which the order's tie-break reads: at n = 16 equal consensus timestamps are common). Equal
+    to the compact columns on the same two ranges, and to the oracle fed the same two batches."""
+    from babble_amd.hashgraph import compact_columns, pack_columns
+    n, E, E0 = 16, 70000, 4000
+    t = _with_nil(gtrace.gossip(n, E, 31, stale_prob=0.1, stale_depth=3))
+    cols = compact_columns(t)
+    head, tail = {k: v[:E0] for k, v in cols.items()}, {k: v[E0:] for k, v in cols.items()}
+    a = _hg(n, E)
+    assert a.insert_events_packed(pack_columns(head, 0)) == E0
+    a.RunConsensus()
+    assert a.insert_and_run_packed(pack_columns(tail, E0)) == E - E0
+    b = _hg(n, E)
+    assert b.insert_events32(cols, 0, E0) == E0
+    b.RunConsensus()
+    assert b.insert_and_run32(cols, E0, E) == E - E0
+    _same(a, b)
+    o = hgref.Oracle(n)
+    o.insert_trace(t, 0, E0)
+    o.run_consensus()
+    o.insert_trace(t, E0, E)
+    o.run_consensus()
+    compare(a, o, t, hashes=False)
+
+
+def test_packed_plain_insert_above_the_one_copy_size():
+    """hgx_insert_events_packed of more than 65 536 events: every column, the payload included, staged
+    by a copy of its own (no other test stages the packed payload that way), with a non-empty
+    exception list. Equal to hgx_insert_events32 of the same columns."""
+    from babble_amd.hashgraph import compact_columns, pack_columns
+    n, E = 16, 66000
+    cols = compact_columns(_with_nil(gtrace.gossip(n, E, 32, stale_prob=0.1, stale_depth=3)))
+    cols = _far_parents(cols, every=150, back=65600)
+    pk = pack_columns(cols, 0)
+    assert len(pk["exc_pos"]) > 0
+    a = _hg(n, E)
+    assert a.insert_events_packed(pk) == E
+    a.RunConsensus()
+    b = _hg(n, E)
+    assert b.insert_events32(cols) == E
+    b.RunConsensus()
+    _same(a, b)
