@@ -8,7 +8,9 @@ break is S, consensus_sorter.go) runs on real signatures. Checked:
   * the batch stops at the first bad signature with Go's "Invalid signature", and the
     signature's failure comes before the parent checks of the same event;
   * a creator key that is not a P-256 point panics like the reference (nil key);
-  * the device-resident variant, and the "keys not set" error."""
+  * the device-resident variant, and the "keys not set" error;
+  * a trace signed by construction (tests/p256ref.py) under the keys G, -G, 256^5 G and x = 0, whose
+    digits take the verify's doubling / cancelling branches on the context's own tables."""
 import hashlib
 
 import numpy as np
@@ -44,6 +46,77 @@ def test_signed_trace_accepted_and_bit_exact(n, E, seed):
     for k in ("round", "witness", "famous", "rr", "cts"):
         assert np.array_equal(np.asarray(a[k]), np.asarray(b[k])), k
     assert list(a["order"]) == list(b["order"])
+
+
+def _forged(E, seed):
+    """A 4-participant trace signed without private keys (tests/p256ref.py forge) under the keys G, -G,
+    256^5 G and the point with x = 0; every third event of the first three creators has the digits that
+    make the context's own comb tables hit k_p256_verify's doubling branch (G, 256^5 G) or cancel to
+    infinity and restart (-G). Returns the trace, keys, digests, r and the events that take a branch."""
+    import p256ref as ref
+    G, N, nG = ref.G, ref.N, ref.neg(ref.G)
+    pts = [G, nG, ref.comb_mul(1 << 40, G), ref.lift(0)]
+    t = gtrace.gossip(4, E, seed, stale_prob=0.1, stale_depth=2)
+    rng = np.random.default_rng(seed)
+
+    def scalar():
+        return int.from_bytes(rng.bytes(32), "big") % (N - 1) + 1
+
+    def above(v, j):
+        return v >> (8 * j) << (8 * j)
+
+    dig, r, s = (np.zeros((t.E, 32), np.uint8) for _ in range(3))
+    branch = {"dbl": [], "opp": []}
+    for i in range(t.E):
+        c = int(t.creator[i])
+        u1, u2, b = scalar(), scalar(), 1 + int(rng.integers(255))
+        if i % 3 == 0 and c < 3:
+            j = 5 if c == 2 else 0
+            u1, u2 = above(u1, j + 1) | b << (8 * j), above(u2, j + 1) | b
+        sig = ref.forge(pts[c], u1, u2, mul=ref.comb_mul)
+        ev = ref.comb_events(pts[c], *sig)
+        for k in branch:
+            if any(x.startswith(k + "@") for x in ev):
+                assert "final-inf" not in ev
+                branch[k].append(i)
+        for col, v in zip((dig, r, s), sig):
+            col[i] = np.frombuffer(v.to_bytes(32, "big"), np.uint8)
+    t.s = s.copy()
+    keys = np.stack([np.frombuffer(ref.pub65(q), np.uint8) for q in pts])
+    return t, keys, dig, r, branch
+
+
+def test_forged_signatures_through_the_context_tables():
+    """Engine::set_keys + insert_verified run the same kernels on the context's own tables, the key
+    index being the event's creator: rare-branch signatures there, then one whose u1 G + u2 Q is
+    the point at infinity."""
+    import p256ref as ref
+    from babble_amd._lib import HgxError
+    t, keys, dig, r, branch = _forged(300, 11)
+    assert len(branch["dbl"]) >= 20 and len(branch["opp"]) >= 10
+    assert len({bytes(x) for x in t.s}) == t.E
+    h = _hg(4, t.E)
+    h.set_participant_keys(keys)
+    assert h.insert_verified(t, dig, r) == t.E
+    h.RunConsensus()
+    a, b = h.results(), hgref.oracle_run(t).results()
+    for k in ("round", "witness", "famous", "rr", "cts"):
+        assert np.array_equal(np.asarray(a[k]), np.asarray(b[k])), k
+    assert list(a["order"]) == list(b["order"])
+    # u1 = u2 under -G: every position cancels, the sum is infinity, no r verifies
+    k0 = int(np.nonzero(t.creator == 1)[0][40])
+    e0, r0, s0 = ref.forge(ref.neg(ref.G), 0x1234567, 0x1234567, r=int.from_bytes(bytes(r[k0]), "big"))
+    assert ref.comb_events(ref.neg(ref.G), e0, r0, s0)[-1] == "final-inf"
+    dd, ss = dig.copy(), t.s.copy()
+    dd[k0] = np.frombuffer(e0.to_bytes(32, "big"), np.uint8)
+    ss[k0] = np.frombuffer(s0.to_bytes(32, "big"), np.uint8)
+    t2 = gtrace.GossipTrace(**{**t.__dict__, "s": ss})
+    h = _hg(4, t.E)
+    h.set_participant_keys(keys)
+    with pytest.raises(HgxError) as ei:
+        h.insert_verified(t2, dd, r)
+    assert ei.value.msg == "Invalid signature" and ei.value.code == 104
+    assert ei.value.inserted == k0 and h.num_events() == k0
 
 
 def test_first_bad_signature_stops_the_batch():

@@ -9,9 +9,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VEC = os.path.join(ROOT, "tests", "golden", "p256_vectors.txt")
 
 
-def load_vectors():
+def load_vectors(path=VEC):
     rows = []
-    with open(VEC) as f:
+    with open(path) as f:
         for line in f:
             pub, dg, r, s, exp, kok, tag = line.split()
             rows.append((bytes.fromhex(pub), bytes.fromhex(dg), bytes.fromhex(r), bytes.fromhex(s), int(exp),
