@@ -334,13 +334,16 @@ bool launch_cts_pipe(hipStream_t s, const DevArrays& a, int c_lo, int c_cnt, int
 // coalesced load whose lines are used whole (k_cts_tile's instruction touches 8 columns for
 // 16 bytes each), and since firstDescendants are monotone along a chain the TP timestamp
 // gathers of a chain fall into a few lines. The per-chain terms are wave-uniform (read from a
-// lane). The gathered values go to LDS as k_cts_tile's 32-bit offsets, vals[c][e]; phase 2 is
-// k_cts_tile's: one wave per event, radix select of element floor(m/2).
+// lane). The gathered values go to LDS as k_cts_tile's 32-bit offsets, vals[c][e]; phase 2 is one
+// wave per event, radix select of element floor(m/2). With two blocks per CU that select is bound
+// by the instructions of its dependent chain, so it is wave_select_kth32_top's (6-bit digits from
+// the top of the range, one bin per lane, exit on a bin of one) and not k_cts_tile's.
 // Membership (WLAT[(rr, tc)][c] >= Index) needs the row of the event's round received; rr is
 // non-decreasing along a chain and TP positions span a few rounds, so the block stages the K
 // rows from its smallest rr in LDS (loads issued beside the gathers) and an event beyond them
 // reads its row from global memory.
-// Measured at c3: 6.46 ms against k_cts_tile's 7.0; 3.3 ms without the selects.
+// Measured at c3: round 9 6.46 ms against k_cts_tile's 7.0, 3.3 ms without the selects;
+// round 11 5.25 ms against 6.50 in the same job, 2.85 without the selects.
 constexpr int kRowKMax = 8;   // staged WLAT rows at most
 constexpr int kRowTP = 64;    // positions per block = lanes of a wave (32 with two chains per instruction: c3 7.13 - 7.24 ms, removed)
 constexpr int kRowD = 16;     // chain instructions in flight per wave (4: 6.55, 8: 6.63 - 6.66, 32: 6.57 ms)
@@ -506,14 +509,14 @@ __global__ void __launch_bounds__(64 * NW) k_cts_row(const int32_t* __restrict__
         for (int q = 0; q < CPL; q++) {
             const int c = lane + 64 * q;
             ok[q] = (mem[e2][c >> 3] >> (c & 7)) & 1u;
-            m += __popcll(__ballot(ok[q]));
+            m += __popcll(__builtin_amdgcn_ballot_w64(ok[q]));
         }
         int64_t res;
         if (!e_ovf[e2]) {
             uint32_t v[CPL];
 #pragma unroll
             for (int q = 0; q < CPL; q++) v[q] = vals[(lane + 64 * q) * LD + e2];
-            const uint32_t u = wave_select_kth32<CPL>(v, ok, m / 2, whist);
+            const uint32_t u = wave_select_kth32_top<CPL>(v, ok, m / 2, whist);
             res = e_ts[e2] + (int64_t)(int32_t)(u ^ 0x80000000u);
         } else {   // rare: offsets beyond 32 bits -> regather and select in 64 bits
             uint64_t v[CPL];

@@ -262,6 +262,76 @@ __device__ uint32_t wave_select_kth32(const uint32_t (&v)[CPL], const bool (&ok)
     return lo + prefix;
 }
 
+// wave_select_kth32 for a caller whose selects are bound by instruction issue (k_cts_row's phase 2:
+// with two blocks per CU a histogram pass costs what the instructions of its dependent chain cost,
+// about as much for 5 active values as for 256). The same result in fewer
+// and shorter passes:
+//  - 6-bit digits, one bin per lane: the chosen bin is the lane whose [excl, incl) of the wave scan
+//    holds rank k, found by one ballot; its count and the values below it are two readlanes, and
+//    there is no walk over a lane's bins;
+//  - digits aligned to the top of the range (shift = bits - 6 first, the last digit takes what is
+//    left), so the first pass spreads the values over all 64 bins whatever the range is;
+//  - the select ends as soon as the chosen bin holds one value (the histogram gives its count; the
+//    value is read from the one lane that still counts), or at shift 0. The consensus timestamps'
+//    offsets span 21 - 23 bits: wave_select_kth32 takes 3 passes on every event, this 2 on 98 % and
+//    3 on the rest (profiles/r11_cts_select/select_passes.txt);
+//  - a value that has left still adds to its bin, but 0: no EXEC masking around the atomics.
+// hist: 64 words owned by this wave. Requires 0 <= K < #valid; every lane returns the result. The
+// pass loop is bounded: six digits cover 32 bits.
+template <int CPL>
+__device__ __forceinline__ uint32_t wave_select_kth32_top(const uint32_t (&v)[CPL], const bool (&ok)[CPL], int K,
+                                                          uint32_t* __restrict__ hist) {
+    constexpr int DB = 6;   // 1 << DB bins = lanes of a wave
+    const int lane = lane_id();
+    uint32_t lo = 0xffffffffu, hi = 0;
+#pragma unroll
+    for (int q = 0; q < CPL; q++)
+        if (ok[q]) { lo = min(lo, v[q]); hi = max(hi, v[q]); }
+    lo = wave_reduce_min_u32(lo);
+    hi = wave_reduce_max_u32(hi);
+    if (hi <= lo) return lo;   // (all equal; no valid value: lo = 0xffffffff)
+    int top = 32 - __clz((int)(hi - lo));   // bits of v - lo not yet resolved
+    uint32_t d[CPL], inc[CPL];
+#pragma unroll
+    for (int q = 0; q < CPL; q++) { d[q] = v[q] - lo; inc[q] = ok[q] ? 1u : 0u; }
+    uint32_t prefix = 0, k = (uint32_t)K;
+#pragma unroll 1
+    for (int pass = 0; pass < (32 + DB - 1) / DB; pass++) {
+        const int shift = top > DB ? top - DB : 0;
+        uint32_t dig[CPL];
+#pragma unroll
+        for (int q = 0; q < CPL; q++) dig[q] = __builtin_amdgcn_ubfe(d[q], (uint32_t)shift, (uint32_t)(top - shift));
+        hist[lane] = 0;
+        wave_lds_fence();
+#pragma unroll
+        for (int q = 0; q < CPL; q++) atomicAdd(&hist[dig[q]], inc[q]);
+        wave_lds_fence();
+        const uint32_t h = hist[lane];
+        wave_lds_fence();
+        const uint32_t incl = wave_scan_add_u32(h);
+        const uint32_t excl = incl - h;
+        const uint64_t bm = __builtin_amdgcn_ballot_w64(k >= excl) & __builtin_amdgcn_ballot_w64(k < incl);
+        const int bucket = bm ? (int)__builtin_ctzll(bm) : 0;   // (k < #counted: bm has one bit)
+        k -= (uint32_t)__builtin_amdgcn_readlane((int)excl, bucket);
+        const uint32_t cnt = (uint32_t)__builtin_amdgcn_readlane((int)h, bucket);
+        prefix |= (uint32_t)bucket << shift;
+        if (shift == 0) break;
+#pragma unroll
+        for (int q = 0; q < CPL; q++) inc[q] = dig[q] == (uint32_t)bucket ? inc[q] : 0u;
+        if (cnt == 1u) {   // the value alone in its bin
+            uint32_t r = lo + prefix;
+#pragma unroll
+            for (int q = 0; q < CPL; q++) {
+                const uint64_t b = __builtin_amdgcn_ballot_w64(inc[q] != 0u);
+                if (b) r = (uint32_t)__builtin_amdgcn_readlane((int)v[q], (int)__builtin_ctzll(b));
+            }
+            return r;
+        }
+        top = shift;
+    }
+    return lo + prefix;
+}
+
 // The same k-th smallest by bisection on the value: each step counts the valid values <= mid with
 // CPL compares whose ballots are popcounted in SGPRs (no LDS, no atomics). For rows whose values
 // crowd into a few buckets (the witnesses' lastAncestors of one chain in k_threshold span a few
