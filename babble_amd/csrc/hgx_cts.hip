@@ -334,16 +334,29 @@ bool launch_cts_pipe(hipStream_t s, const DevArrays& a, int c_lo, int c_cnt, int
 // coalesced load whose lines are used whole (k_cts_tile's instruction touches 8 columns for
 // 16 bytes each), and since firstDescendants are monotone along a chain the TP timestamp
 // gathers of a chain fall into a few lines. The per-chain terms are wave-uniform (read from a
-// lane). The gathered values go to LDS as k_cts_tile's 32-bit offsets, vals[c][e]; phase 2 is one
-// wave per event, radix select of element floor(m/2). With two blocks per CU that select is bound
-// by the instructions of its dependent chain, so it is wave_select_kth32_top's (6-bit digits from
-// the top of the range, one bin per lane, exit on a bin of one) and not k_cts_tile's.
+// lane). The gathered values go to LDS as k_cts_tile's 32-bit offsets, vals[c][e]; phase 2 is the
+// radix select of element floor(m/2), eight events per wave: 8 lanes per event, NPAD / 8 values per
+// lane (group8_select_kth32_top, hgx_device.h: wave_select_kth32_top's arithmetic per event, 6-bit
+// digits from the top of the event's range, exit on a bin of one). Wave w takes the events it took one
+// at a time before, e = w + 8s (four waves: two groups, w and w + 4); the bins of an event are its own
+// column of vals once the values are in registers, and membership is one word per lane (memw). An event
+// whose offsets need 64 bits takes no part and is done afterwards by one wave, as before.
+// Round 12 (profiles/r12_cts_group): with two blocks per CU phase 2 costs what its LDS
+// atomics cost, a wave instruction about the same whether its lanes add 1, add 0 or are masked off. Kept:
+// the group select with an active mask per lane, and the passes after the first over a list of the
+// values still left (4 atomics per pass instead of 32). Rejected: marking a value that has left by
+// overwriting it, all of them adding to one bin (same-address atomics: slower than one wave per event);
+// EXEC masks around the atomics (0.1 ms, not kept). Not measured: 16-bit bins in the waves' 256 words.
 // Membership (WLAT[(rr, tc)][c] >= Index) needs the row of the event's round received; rr is
 // non-decreasing along a chain and TP positions span a few rounds, so the block stages the K
 // rows from its smallest rr in LDS (loads issued beside the gathers) and an event beyond them
 // reads its row from global memory.
 // Measured at c3: round 9 6.46 ms against k_cts_tile's 7.0, 3.3 ms without the selects;
-// round 11 5.25 ms against 6.50 in the same job, 2.85 without the selects.
+// round 11 5.25 ms against 6.50 in the same job, 2.85 without the selects; round 12 FindOrder's device time (this
+// kernel and 2.5 ms of sorting) 6.85 ms against 7.75 in the same job, the kernel itself 4.35 - 4.41 ms against
+// 5.28 - 5.37 warm and 4.84 against 5.41 as a process's first dispatch (SQ_LDS_IDX_ACTIVE 1.13 -> 0.88 G,
+// SQ_INSTS_VALU 2.26 -> 2.21 G). The c3 step gained 0.75 - 1.07 ms in five jobs; that was three times the
+// parent's range in one of them (profiles/r12_cts_group/README.md).
 constexpr int kRowKMax = 8;   // staged WLAT rows at most
 constexpr int kRowTP = 64;    // positions per block = lanes of a wave (32 with two chains per instruction: c3 7.13 - 7.24 ms, removed)
 constexpr int kRowD = 16;     // chain instructions in flight per wave (4: 6.55, 8: 6.63 - 6.66, 32: 6.57 ms)
@@ -366,15 +379,17 @@ __global__ void __launch_bounds__(64 * NW) k_cts_row(const int32_t* __restrict__
     constexpr int NI = CW;                // chain instructions per wave: instruction k takes chain wc0 + k
     constexpr int D = DREQ < NI ? DREQ : NI;
     constexpr int NB = NI / D;
-    constexpr int MB = NPAD / 8;          // membership bytes per event
-    static_assert(NI % D == 0 && NI % 8 == 0 && NI <= 64, "k_cts_row: batches and membership bytes");
+    constexpr int VPL = NPAD / 8;         // phase 2: values per lane, 8 lanes per event
+    static_assert(NI % D == 0 && NI % 8 == 0 && NI <= 32 && 8 % NW == 0, "k_cts_row: batches, membership words, groups");
     constexpr int RG = 64 * NW / NPAD;    // staged rows loaded at once (thread t: word t % NPAD of row t / NPAD)
     constexpr int KL = kRowKMax / RG;     // staging loads per thread
     static_assert(RG >= 1 && kRowKMax % RG == 0, "k_cts_row: staging loads");
     // [NPAD][LD] offsets + 2^31 | wl[K][n + 1], reused by phase 2 as the waves' histograms [NW][256]
     extern __shared__ __attribute__((aligned(16))) uint32_t vals[];
     int32_t* wl = (int32_t*)(vals + NPAD * LD);
-    __shared__ uint8_t mem[TP][MB];
+    // memw[l * LD + e]: bit q = chain l + 8q is a member of event e (phase 2's lane (e, l) holds those
+    // chains; with the stride LD the 64 lanes of either phase hit 64 banks)
+    __shared__ uint32_t memw[8 * LD];
     __shared__ int32_t e_row[TP];
     __shared__ int64_t e_ts[TP];
     __shared__ int32_t e_ovf[TP];
@@ -426,6 +441,7 @@ __global__ void __launch_bounds__(64 * NW) k_cts_row(const int32_t* __restrict__
         e_ts[e] = base;
         e_ovf[e] = 0;
     }
+    for (int w = (int)threadIdx.x; w < 8 * LD; w += 64 * NW) memw[w] = 0;
     cp_lds_barrier();
     uint32_t bmin = s_min[0];
 #pragma unroll
@@ -495,41 +511,52 @@ __global__ void __launch_bounds__(64 * NW) k_cts_row(const int32_t* __restrict__
         const int live = n - wc0;
         if (live < NI) okm &= live > 0 ? ((uint64_t)1 << live) - 1 : 0;
         if (!evi) okm = 0;
+        // the wave's chains wc0 + l + 8j are bits wc0 / 8 + j of word l: bits l, l + 8, l + 16, l + 24 of okm,
+        // gathered by a multiply (the partial products land on distinct bits, none carries into 28..31)
+        const uint32_t ok32 = (uint32_t)okm;
 #pragma unroll
-        for (int q = 0; q < NI / 8; q++) mem[e][wc0 / 8 + q] = (uint8_t)(okm >> (8 * q));
+        for (int l = 0; l < 8; l++)
+            atomicOr(&memw[l * LD + e], ((((ok32 >> l) & 0x01010101u) * 0x10204080u) >> 28) << (wc0 / 8));
         if (ovm & okm) e_ovf[e] = 1;
     }
     __syncthreads();
-    // phase 2: one wave per event
-    for (int e2 = wave; e2 < TP; e2 += NW) {
-        if (e_row[e2] < 0) continue;   // wave-uniform
-        bool ok[CPL];
-        int m = 0;
+    // phase 2: eight events per wave, 8 lanes each. Lane (gs, gl) of group vw = wave + NW * grp belongs to
+    // event vw + 8 * gs and holds chains gl + 8q: a load of vals[c][e] hits 64 banks. The bins of an event
+    // are its own column of vals (rows 0..63), which no other lane reads once the values are in registers.
+    const int gs = lane >> 3, gl = lane & 7;
+    for (int grp = 0; grp < 8 / NW; grp++) {
+        const int vw = wave + NW * grp, e2 = vw + 8 * gs;
+        const bool has = e_row[e2] >= 0, wide = e_ovf[e2] != 0;
+        if (!__builtin_amdgcn_ballot_w64(has)) continue;   // no event in the group
+        const bool part = has && !wide;   // absent and 64-bit events take no part: no member
+        if (__builtin_amdgcn_ballot_w64(part)) {
+            uint32_t* hcol = vals + e2;
+            const uint32_t member = part ? memw[gl * LD + e2] : 0u;
+            uint32_t v[VPL];
 #pragma unroll
-        for (int q = 0; q < CPL; q++) {
-            const int c = lane + 64 * q;
-            ok[q] = (mem[e2][c >> 3] >> (c & 7)) & 1u;
-            m += __popcll(__builtin_amdgcn_ballot_w64(ok[q]));
+            for (int q = 0; q < VPL; q++) v[q] = hcol[(gl + 8 * q) * LD];
+            const uint32_t u = group8_select_kth32_top<VPL, LD>(v, member, hcol, whist + 32 * gs, gl);
+            if (part && gl == 0) p_cts[ps + e2] = e_ts[e2] + (int64_t)(int32_t)(u ^ 0x80000000u);
         }
-        int64_t res;
-        if (!e_ovf[e2]) {
-            uint32_t v[CPL];
-#pragma unroll
-            for (int q = 0; q < CPL; q++) v[q] = vals[(lane + 64 * q) * LD + e2];
-            const uint32_t u = wave_select_kth32_top<CPL>(v, ok, m / 2, whist);
-            res = e_ts[e2] + (int64_t)(int32_t)(u ^ 0x80000000u);
-        } else {   // rare: offsets beyond 32 bits -> regather and select in 64 bits
+        // rare: offsets beyond 32 bits -> one wave per event, regather and select in 64 bits
+        for (uint64_t todo = __builtin_amdgcn_ballot_w64(has && wide) & 0x0101010101010101ull; todo; todo &= todo - 1) {
+            const int e3 = vw + (int)__builtin_ctzll(todo);   // (bit 8 * gs: event vw + 8 * gs)
+            const uint32_t mw = memw[gl * LD + e3];
+            bool ok[CPL];
             uint64_t v[CPL];
+            int m = 0;
 #pragma unroll
             for (int q = 0; q < CPL; q++) {
-                const int c = lane + 64 * q;
+                const int c = lane + 64 * q;   // = gl + 8 * (gs + 8q)
+                ok[q] = (mw >> (gs + 8 * q)) & 1u;
+                m += __popcll(__builtin_amdgcn_ballot_w64(ok[q]));
                 int64_t x = 0;
-                if (ok[q]) x = p_ts[c_off[gb + c] - c_base[gb + c] + Coord<CT>::fd(FDT[(size_t)c * Pcap + ps + e2])];
+                if (ok[q]) x = p_ts[c_off[gb + c] - c_base[gb + c] + Coord<CT>::fd(FDT[(size_t)c * Pcap + ps + e3])];
                 v[q] = (uint64_t)x ^ 0x8000000000000000ull;
             }
-            res = (int64_t)(wave_select_kth<CPL>(v, ok, m / 2, whist) ^ 0x8000000000000000ull);
+            const int64_t res = (int64_t)(wave_select_kth<CPL>(v, ok, m / 2, whist) ^ 0x8000000000000000ull);
+            if (lane == 0) p_cts[ps + e3] = res;
         }
-        if (lane == 0) p_cts[ps + e2] = res;
     }
 }
 
@@ -538,7 +565,7 @@ static bool cts_row_launch(hipStream_t s, const DevArrays& a, int c_lo, int c_cn
                            int max_cnt, int R, int k_rows) {
     constexpr int TP = kRowTP, NW = row_waves(NPAD);
     // two blocks per CU at NPAD = 256: the block's static LDS, vals and the staged rows within 79 KB
-    constexpr size_t kStatic = (size_t)TP * (NPAD / 8) + (size_t)TP * 16 + 4 * NW;
+    constexpr size_t kStatic = (size_t)8 * (TP + 1) * 4 + (size_t)TP * 16 + 4 * NW;
     const size_t fixed = (size_t)NPAD * (TP + 1) * 4, row = (size_t)(n + 1) * 4;
     const int room = (int)(((size_t)79 * 1024 - kStatic - fixed) / row);
     const int K = k_rows > 0 ? std::min(k_rows, kRowKMax) : std::max(1, std::min(room, kRowKMax));

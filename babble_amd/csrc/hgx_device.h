@@ -332,6 +332,181 @@ __device__ __forceinline__ uint32_t wave_select_kth32_top(const uint32_t (&v)[CP
     return lo + prefix;
 }
 
+// Reductions and the inclusive scan over groups of 8 consecutive lanes, on DPP: quad_perm [1,0,3,2],
+// quad_perm [2,3,0,1], row_half_mirror (lane i <-> 7 - i of its half row). Every lane of a group gets
+// the group's result. All 64 lanes must be active.
+template <int CTRL, int BANK = 0xf>
+__device__ __forceinline__ uint32_t dpp_mov0(uint32_t x) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, BANK, false);
+}
+#define HGX_DPP_GROUP8(x, OP)                    \
+    do {                                         \
+        x = OP(x, dpp_mov0<0xB1>(x));            \
+        x = OP(x, dpp_mov0<0x4E>(x));            \
+        x = OP(x, dpp_mov0<0x141>(x));           \
+    } while (0)
+#define HGX_OP_OR(a, b) ((a) | (b))
+__device__ __forceinline__ uint32_t group8_add_u32(uint32_t x) { HGX_DPP_GROUP8(x, HGX_OP_ADD); return x; }
+__device__ __forceinline__ uint32_t group8_or_u32(uint32_t x) { HGX_DPP_GROUP8(x, HGX_OP_OR); return x; }
+__device__ __forceinline__ uint32_t group8_min_u32(uint32_t x) { HGX_DPP_GROUP8(x, HGX_OP_MIN); return x; }
+__device__ __forceinline__ uint32_t group8_max_u32(uint32_t x) { HGX_DPP_GROUP8(x, HGX_OP_MAX); return x; }
+// l = lane & 7. row_shr 1 and 2 cross the groups of a row of 16 (masked by l), row_shr 4 is enabled in the
+// upper quad of each group only (bank mask 0xA); a lane without a source reads 0.
+__device__ __forceinline__ uint32_t group8_scan_add_u32(uint32_t x, int l) {
+    const uint32_t y1 = dpp_mov0<0x111>(x);   // (read by every lane: a DPP source must be an active lane)
+    x += l >= 1 ? y1 : 0u;
+    const uint32_t y2 = dpp_mov0<0x112>(x);
+    x += l >= 2 ? y2 : 0u;
+    x += dpp_mov0<0x114, 0xA>(x);
+    return x;
+}
+
+
+// wave_select_kth32_top for eight events side by side: 8 consecutive lanes per event (l = lane & 7),
+// VPL values per lane, one instruction serves eight selects. Same arithmetic per event (values rebased
+// to the event's minimum, 6-bit digits from the top of the event's range, exit on a bin of one or at
+// shift 0, at most six passes), with the event's minimum, top, shift, rank and prefix in VGPRs.
+struct Group8Sel {
+    uint32_t lo, res, prefix, k;   // minimum, result so far, digits chosen, rank among what still counts
+    int top;                       // bits of v - lo not yet resolved
+    bool live;                     // still selecting (the same in the 8 lanes of an event)
+};
+
+// One histogram pass over d[q] = v - lo; bit q of act: the value still counts (act = 0: the lanes run
+// along and add 0, there is no EXEC masking around the atomics). Returns the count of the chosen bin and
+// leaves in act the values inside it.
+//  - hcol: the event's 64 bins, hcol[b * LD], LDS words that only this event's lanes touch. Lane l owns
+//    bins l + 8t, t = 0..7: with LD = 65 and the events of a wave 8 columns apart, the 64 lanes of a
+//    clear or a read hit 64 banks (bins 8l..8l+7 would put 8 lanes on each bank). The chosen bin is found
+//    by walking the 8 row totals (three DPP steps each), then by a scan over the 8 lanes of that row;
+//    the owner hands bin, rank below and count to its group in one packed word.
+//  - the winner of a bin of one is the minimum over the values that still count.
+template <int NV, int LD>
+__device__ __forceinline__ uint32_t group8_select_pass(const uint32_t (&d)[NV], uint32_t& act, Group8Sel& s,
+                                                       uint32_t* hcol, int l) {
+    constexpr int DB = 6;
+    const int shift = s.top > DB ? s.top - DB : 0;
+    const uint32_t width = (uint32_t)(s.top - shift);   // <= DB: every digit is a bin of hcol
+    // bin b of the event, as a byte offset from hcol: one v_mad_u32_u24
+    auto bin = [&](uint32_t b) -> uint32_t* { return (uint32_t*)((char*)hcol + __umul24(b, (uint32_t)(LD * 4))); };
+#pragma unroll
+    for (int t = 0; t < 8; t++) hcol[(l + 8 * t) * LD] = 0;
+    wave_lds_fence();
+#pragma unroll
+    for (int q = 0; q < NV; q++) atomicAdd(bin(__builtin_amdgcn_ubfe(d[q], (uint32_t)shift, width)), (act >> q) & 1u);
+    wave_lds_fence();
+    uint32_t h[8];
+#pragma unroll
+    for (int t = 0; t < 8; t++) h[t] = hcol[(l + 8 * t) * LD];
+    wave_lds_fence();
+    // the row of 8 bins that holds rank k: the last whose exclusive prefix is <= k
+    uint32_t acc = 0, below = 0, hsel = 0, tsel = 0;
+#pragma unroll
+    for (int t = 0; t < 8; t++) {
+        const bool c = s.k >= acc;
+        below = c ? acc : below;
+        hsel = c ? h[t] : hsel;
+        tsel = c ? (uint32_t)t : tsel;
+        acc += group8_add_u32(h[t]);
+    }
+    const uint32_t k1 = s.k - below;
+    const uint32_t incl = group8_scan_add_u32(hsel, l), excl = incl - hsel;
+    const bool own = k1 >= excl && k1 < incl;   // one lane of a selecting event
+    const uint32_t pk = group8_or_u32(own ? (tsel * 8 + (uint32_t)l) | excl << 6 | hsel << 16 : 0u);
+    const uint32_t bucket = pk & 63u, cnt = pk >> 16;
+    s.k = k1 - ((pk >> 6) & 1023u);
+    s.prefix |= bucket << shift;
+    const bool last = shift == 0, one = cnt == 1u;
+    if (__builtin_amdgcn_ballot_w64(s.live && !last)) {
+        uint32_t keep = 0;
+#pragma unroll
+        for (int q = 0; q < NV; q++) keep |= __builtin_amdgcn_ubfe(d[q], (uint32_t)shift, width) == bucket ? 1u << q : 0u;
+        act &= keep;
+    }
+    if (__builtin_amdgcn_ballot_w64(s.live && !last && one)) {   // the value alone in its bin
+        uint32_t w = 0xffffffffu;
+#pragma unroll
+        for (int q = 0; q < NV; q++) w = min(w, d[q] | ~(uint32_t)__builtin_amdgcn_sbfe((int)act, q, 1));
+        w = group8_min_u32(w);
+        s.res = s.live && !last && one ? s.lo + w : s.res;
+    }
+    s.res = s.live && last ? s.lo + s.prefix : s.res;
+    s.live = s.live && !last && !one;
+    act = s.live ? act : 0u;
+    s.top = shift;
+    return cnt;
+}
+
+// The select of eight events. v[q], bit q of `member`: the lane's values and which of them count.
+// member = 0 in all 8 lanes: the event takes no part (its lanes run along and return 0xffffffff).
+// Requires #members >= 1 otherwise; the rank is #members / 2. v is overwritten. hcol: see above. list: CAP
+// = 32 words of LDS per event, the event's lanes only (any values of the event's own may be left in it).
+// With two blocks per CU a pass costs what its LDS atomics cost, about as much for a lane that adds 0 as
+// for one that adds 1. After the first pass few values are left (17 of 256 at the
+// median of a gossip trace), so when every event of the wave that still selects has at most CAP of them,
+// they are written to `list` in lane order, each lane takes CAP / 8 back, and the later passes issue CAP /
+// 8 atomics instead of VPL. Otherwise (two-valued offsets, say) all passes run over the VPL values. The pass
+// loops end when a ballot shows no event of the wave still selecting. Every lane of an event returns its
+// result.
+template <int VPL, int LD>
+__device__ __forceinline__ uint32_t group8_select_kth32_top(uint32_t (&v)[VPL], uint32_t member, uint32_t* hcol,
+                                                            uint32_t* list, int l) {
+    constexpr int DB = 6, PASSES = (32 + DB - 1) / DB, CAP = 32, LV = CAP / 8;
+    uint32_t lo = 0xffffffffu, hi = 0;
+#pragma unroll
+    for (int q = 0; q < VPL; q++) {
+        const uint32_t in = (uint32_t)__builtin_amdgcn_sbfe((int)member, q, 1);   // all ones: counts
+        lo = min(lo, v[q] | ~in);
+        hi = max(hi, v[q] & in);
+    }
+    lo = group8_min_u32(lo);
+    hi = group8_max_u32(hi);
+    const uint32_t m = group8_add_u32((uint32_t)__popc(member));
+    Group8Sel s;
+    s.lo = lo;
+    s.res = lo;            // (all equal, or no member)
+    s.prefix = 0;
+    s.k = m >> 1;
+    s.live = hi > lo;
+    s.top = s.live ? 32 - __clz((int)(hi - lo)) : 0;
+#pragma unroll
+    for (int q = 0; q < VPL; q++) v[q] -= lo;
+    uint32_t act = s.live ? member : 0u;
+    if (!__builtin_amdgcn_ballot_w64(s.live)) return s.res;
+    const uint32_t cnt = group8_select_pass<VPL, LD>(v, act, s, hcol, l);
+    if (!__builtin_amdgcn_ballot_w64(s.live)) return s.res;
+    if (VPL > LV && !__builtin_amdgcn_ballot_w64(s.live && cnt > (uint32_t)CAP)) {
+        const uint32_t mine = (uint32_t)__popc(act);
+        uint32_t pos = group8_scan_add_u32(mine, l) - mine;
+        // VPL stores under EXEC, once, for VPL - LV fewer atomics in every later pass: a store is not the
+        // 20 cycles of an atomic, and at c3 FindOrder went 7.3 -> 6.85 ms with the list (sweep.txt job 3)
+#pragma unroll
+        for (int q = 0; q < VPL; q++)
+            if ((act >> q) & 1u) list[pos++ & (CAP - 1)] = v[q];   // (pos < cnt <= CAP)
+        wave_lds_fence();
+        uint32_t w[LV], wact = 0;
+#pragma unroll
+        for (int j = 0; j < LV; j++) {
+            w[j] = list[l + 8 * j];
+            wact |= (uint32_t)(l + 8 * j) < cnt ? 1u << j : 0u;
+        }
+        wact = s.live ? wact : 0u;
+        wave_lds_fence();
+#pragma unroll 1
+        for (int pass = 1; pass < PASSES; pass++) {
+            group8_select_pass<LV, LD>(w, wact, s, hcol, l);
+            if (!__builtin_amdgcn_ballot_w64(s.live)) break;
+        }
+    } else {
+#pragma unroll 1
+        for (int pass = 1; pass < PASSES; pass++) {
+            group8_select_pass<VPL, LD>(v, act, s, hcol, l);
+            if (!__builtin_amdgcn_ballot_w64(s.live)) break;
+        }
+    }
+    return s.res;
+}
+
 // The same k-th smallest by bisection on the value: each step counts the valid values <= mid with
 // CPL compares whose ballots are popcounted in SGPRs (no LDS, no atomics). For rows whose values
 // crowd into a few buckets (the witnesses' lastAncestors of one chain in k_threshold span a few
