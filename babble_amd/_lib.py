@@ -77,6 +77,11 @@ class hgx_wire_out(C.Structure):
     _fields_ = [(nm, C.c_void_p) for nm, _, _ in WIRE_OUT_COLUMNS]
 
 
+class hgx_wire_body_out(C.Structure):
+    _fields_ = [("sig_r", C.c_void_p), ("tx_off", C.c_void_p), ("tx_cap", C.c_int64), ("tx_bytes", C.c_void_p),
+                ("bytes_cap", C.c_int64)]
+
+
 def ptr(a: np.ndarray):
     assert a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(C.c_void_p)
@@ -186,6 +191,16 @@ def lib():
     _sig(L, "hgx_wire_info", i32, [p, i64, i64, p, p, p])
     _sig(L, "hgx_read_wire_info", i32, [p, i32, i64, i32, i64, p, p, E])
     _sig(L, "hgx_diff_wire", i32, [p, i32, p, i64, p, i64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), E])
+    _sig(L, "hgx_keep_bodies", i32, [p, i64, i64, E])
+    _sig(L, "hgx_bodies_state", i32, [p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)])
+    _sig(L, "hgx_get_event_bodies", i32, [p, p, i64, p, p, p, i64, p, i64, C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int64), E])
+    _sig(L, "hgx_block_transactions", i32, [p, i32, i64, p, i64, p, i64, C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_int64), E])
+    _sig(L, "hgx_get_block_hash", i32, [p, i32, i64, p, E])
+    _sig(L, "hgx_block_hash_batch", i32, [i32, p, p, p, p, p, i64, p, E])
+    _sig(L, "hgx_diff_wire_bodies", i32, [p, i32, p, i64, p, C.POINTER(hgx_wire_body_out), i64, C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), E])
     _sig(L, "hgx_get_rounds", i32, [p, i64, i64, p, p, p])
     _sig(L, "hgx_get_received", i32, [p, i64, i64, p, p])
     _sig(L, "hgx_get_coords", i32, [p, i64, p, p])

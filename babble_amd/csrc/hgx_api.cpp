@@ -21,6 +21,7 @@
 
 #include "hgx.h"
 #include "hgx_bodies.h"
+#include "hgx_bodystore.h"
 #include "hgx_diff.h"
 #include "hgx_engine.h"
 #include "hgx_wire_plan.h"
@@ -34,6 +35,8 @@ struct Block {
     int64_t ntx;
     int32_t tx_nil;
     int32_t committed;
+    int32_t has_hash = 0;      // Block.Hash computed when the block was made (a keeping context)
+    uint8_t hash[32] = {};
 };
 
 // growable pinned host array: the consensus order is copied D2H straight into it
@@ -455,6 +458,9 @@ static int32_t finish_insert(hgx_ctx* c, const hgx::InsertOut& out, int64_t* n_i
         c->g_loaded[g] = l;
     }
     c->E = c->eng.E;
+    // a keeping context: events that came without their bodies leave the store lost
+    if (c->eng.bodies_state == hgx::kBodiesComplete && c->eng.bodies_events != c->eng.E)
+        c->eng.bodies_state = hgx::kBodiesLost;
     if (out.accepted > 0) {
         c->mirror_ok = c->chains_ok = false;
         c->rounds_cached = c->recv_cached = false;
@@ -495,6 +501,10 @@ static int32_t finish_insert(hgx_ctx* c, const hgx::InsertOut& out, int64_t* n_i
         case hgx::INS_BAD_KEY:   // elliptic.Unmarshal returned nil; ecdsa.Verify dereferences it
             rc = HGX_ERR_PANIC;
             msg = "runtime error: invalid memory address or nil pointer dereference";
+            break;
+        case hgx::INS_BODY_CAPACITY:
+            rc = HGX_ERR_CAPACITY;
+            msg = "hgx_keep_bodies: the body store could not grow (out of device memory)";
             break;
         case hgx::INS_WIRE_HOLE:   // (a bug: the host plan named a resident event the window kernel did not find)
             rc = HGX_ERR_PANIC;
@@ -1726,6 +1736,18 @@ int32_t hgx_prune_to_frame(hgx_ctx* c, int64_t* old_gid, int64_t cap, int64_t* n
             pl_off.push_back((int64_t)pl_blob.size());
         }
     }
+    // a keeping context: the kept events' bodies into new tables. This can fail (device memory, 4 GiB
+    // in one gather) and changes nothing the context holds, so it comes before anything is dropped
+    bool bodies_large = false;
+    e = c->eng.prune_bodies(&bodies_large);
+    if (e == hipErrorOutOfMemory || bodies_large) {
+        (void)hipGetLastError();
+        set_err(err, HGX_ERR_CAPACITY,
+                bodies_large ? "hgx_prune_to_frame: the kept events' bodies reach 4 GiB (nothing was pruned)"
+                             : "hgx_prune_to_frame: out of device memory for the kept events' bodies (nothing was pruned)");
+        return HGX_ERR_CAPACITY;
+    }
+    if (e != hipSuccess) return dev_err(err, e, "hgx_prune_to_frame");
     for (int64_t k = 0; k < kept && k < cap; k++) old_gid[k] = po.old_gid[(size_t)k];
     // ---- the destructive part: Reset with the frame's roots, then InsertEvent for the staged frame ----
     hgx::InsertOut out;
@@ -2176,6 +2198,33 @@ static int32_t find_order_end_one(hgx_ctx* c, hgx_error* err) {
         e = c->eng.sync();
         if (e != hipSuccess) return dev_err(err, e, "hgx_find_order");
     }
+    // a keeping context: Block.Hash of the call's new blocks (graph-major, rr ascending: the order's own
+    // sequence), from the device-resident order and the body store. Before any host state is committed,
+    // so a failure leaves no block without its hash, and before commitCh sees the blocks
+    // (hgx_get_block_hash works inside the callback)
+    const bool hash_blocks = c->eng.bodies_state == hgx::kBodiesComplete && total > 0 && c->shard_world == 1 && !c->grp;
+    std::vector<uint8_t> hashes;
+    if (hash_blocks) {
+        std::vector<int64_t> brr;
+        std::vector<int32_t> bntx, bnil;
+        for (int g = 0; g < G; g++)
+            for (int32_t rr = 0; rr < R; rr++) {
+                const size_t bi = (size_t)g * R + rr;
+                if (!oh.blk_cnt[bi]) continue;
+                brr.push_back(rr);
+                bntx.push_back((int32_t)oh.blk_ntx[bi]);
+                bnil.push_back((oh.blk_nil[bi] && oh.blk_ntx[bi] == 0) ? 1 : 0);
+            }
+        hashes.resize(brr.size() * 32);
+        bool large = false;
+        e = c->eng.order_block_hashes(total, brr.data(), bntx.data(), bnil.data(), (int64_t)brr.size(), hashes.data(), &large);
+        if (e != hipSuccess) return dev_err(err, e, "hgx_find_order: block hashes");
+        if (large) {
+            set_err(err, HGX_ERR_CAPACITY, "hgx_find_order: the new blocks' transactions or text reach 4 GiB");
+            return HGX_ERR_CAPACITY;
+        }
+    }
+    size_t n_hashed = 0;
     c->arena.used = base_off + (size_t)total;
     // committed blocks (graph, block index): commitCh receives them once the graph state
     // (counters, pending, undetermined) is final for this call
@@ -2202,6 +2251,10 @@ static int32_t find_order_end_one(hgx_ctx* c, hgx_error* err) {
             // NewBlock(rr, first.Transactions()) then append(...): nil iff first nil and nothing appended
             b.tx_nil = (oh.blk_nil[bi] && b.ntx == 0) ? 1 : 0;
             b.committed = b.ntx > 0 ? 1 : 0;   // commitCh only if len(Transactions) > 0
+            if (hash_blocks) {
+                std::memcpy(b.hash, hashes.data() + 32 * n_hashed++, 32);
+                b.has_hash = 1;
+            }
             s.blocks.push_back(b);
             if (b.committed && c->commit_fn) commits.push_back({g, (int64_t)s.blocks.size() - 1});
             s.consensus_tx += b.ntx;
@@ -2602,10 +2655,11 @@ int32_t hgx_wire_info(hgx_ctx* c, int64_t first, int64_t count, int32_t* self_pa
 // node/core.go:147-188) in one call: the host plan sizes the answer from the per-chain mirrors, the
 // device filters and gathers where the events live. The host mirror of the event
 // columns is neither read nor dropped.
-int32_t hgx_diff_wire(hgx_ctx* c, int32_t g, const int32_t* known, int64_t sync_limit, hgx_wire_out* out, int64_t cap,
-                      int64_t* count, int32_t* over_limit, hgx_error* err) {
+static int32_t diff_wire_impl(hgx_ctx* c, int32_t g, const int32_t* known, int64_t sync_limit, hgx_wire_out* out,
+                              int64_t cap, int64_t* count, int32_t* over_limit, hgx_error* err, const char* who,
+                              hgx::Engine::DiffBodies* body) {
     auto invalid = [&](const char* why) {
-        set_err(err, HGX_ERR_INVALID, std::string("hgx_diff_wire: ") + why);
+        set_err(err, HGX_ERR_INVALID, std::string(who) + ": " + why);
         return HGX_ERR_INVALID;
     };
     if (!c || !known || !out || !count) return invalid("bad arguments");
@@ -2631,16 +2685,165 @@ int32_t hgx_diff_wire(hgx_ctx* c, int32_t g, const int32_t* known, int64_t sync_
                                      out->tx_nil, out->hash, out->sig_s, out->root_parent};
     int64_t dev_total = 0;
     const hipError_t e = c->eng.diff_wire(g, known, c->root_index.data() + c0, std::min(cap, plan.total), plan.total,
-                                          cols, &dev_total);
-    if (e != hipSuccess) return dev_err(err, e, "hgx_diff_wire");
+                                          cols, &dev_total, body);
+    if (e != hipSuccess) return dev_err(err, e, who);
     if (dev_total != plan.total) {
-        set_err(err, HGX_ERR_PANIC, "hgx_diff_wire: the device selected " + std::to_string(dev_total) +
+        set_err(err, HGX_ERR_PANIC, std::string(who) + ": the device selected " + std::to_string(dev_total) +
                                         " events, the host plan " + std::to_string(plan.total));
         return HGX_ERR_PANIC;
     }
     *count = plan.total;
     if (over_limit) *over_limit = 0;
     return ok(err);
+}
+
+int32_t hgx_diff_wire(hgx_ctx* c, int32_t g, const int32_t* known, int64_t sync_limit, hgx_wire_out* out, int64_t cap,
+                      int64_t* count, int32_t* over_limit, hgx_error* err) {
+    return diff_wire_impl(c, g, known, sync_limit, out, cap, count, over_limit, err, "hgx_diff_wire", nullptr);
+}
+
+// ---- the resident body store -------------------------------------------
+int32_t hgx_keep_bodies(hgx_ctx* c, int64_t tx_hint, int64_t bytes_hint, hgx_error* err) {
+    if (const char* why = hgx::keep_bodies_check(c != nullptr, c ? c->E : 0, tx_hint, bytes_hint, c && c->grp,
+                                                 c && c->shard_world > 1)) {
+        set_err(err, HGX_ERR_INVALID, std::string("hgx_keep_bodies: ") + why);
+        return HGX_ERR_INVALID;
+    }
+    DeviceGuard dg(c);
+    const hipError_t e = c->eng.bodies_keep(tx_hint, bytes_hint);
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        set_err(err, HGX_ERR_CAPACITY, "hgx_keep_bodies: out of device memory");
+        return HGX_ERR_CAPACITY;
+    }
+    if (e != hipSuccess) return dev_err(err, e, "hgx_keep_bodies");
+    return ok(err);
+}
+
+int32_t hgx_bodies_state(hgx_ctx* c, int64_t* n_events, int64_t* n_tx, int64_t* n_bytes) {
+    if (!c) return 0;
+    if (n_events) *n_events = c->eng.bodies_events;
+    if (n_tx) *n_tx = c->eng.bodies_tx;
+    if (n_bytes) *n_bytes = c->eng.bodies_bytes;
+    return c->eng.bodies_state;
+}
+
+// the consumers' common gate: HGX_ERR_INVALID "<fn>: bodies not known" unless the store is complete
+static int32_t bodies_gate(hgx_ctx* c, hgx_error* err, const char* who) {
+    if (c && c->eng.bodies_state == hgx::kBodiesComplete) return HGX_OK;
+    set_err(err, HGX_ERR_INVALID, std::string(who) + (c ? ": bodies not known" : ": bad arguments"));
+    return HGX_ERR_INVALID;
+}
+
+// a gather's outcome as the three consumers report it
+static int32_t bodies_outcome(hipError_t e, hgx::Engine::BodyFit fit, hgx_error* err, const char* who) {
+    if (e != hipSuccess) return dev_err(err, e, who);
+    if (fit == hgx::Engine::kBodyTooLarge) {
+        set_err(err, HGX_ERR_CAPACITY, std::string(who) + ": 4 GiB or more in one call (ask for fewer events)");
+        return HGX_ERR_CAPACITY;
+    }
+    if (fit != hgx::Engine::kBodyFits) {
+        set_err(err, HGX_ERR_CAPACITY, std::string(who) + ": tx_cap / bytes_cap too small (n_tx and n_bytes are set)");
+        return HGX_ERR_CAPACITY;
+    }
+    return ok(err);
+}
+
+int32_t hgx_get_event_bodies(hgx_ctx* c, const int64_t* gids, int64_t count, uint8_t* sig_r, int32_t* ntx,
+                             int64_t* tx_off, int64_t tx_cap, uint8_t* tx_bytes, int64_t bytes_cap, int64_t* n_tx,
+                             int64_t* n_bytes, hgx_error* err) {
+    const char* who = "hgx_get_event_bodies";
+    if (!c || count < 0 || (count > 0 && !gids) || !n_tx || !n_bytes || tx_cap < 0 || bytes_cap < 0) {
+        set_err(err, HGX_ERR_INVALID, std::string(who) + ": bad arguments");
+        return HGX_ERR_INVALID;
+    }
+    if (bodies_gate(c, err, who)) return HGX_ERR_INVALID;
+    for (int64_t k = 0; k < count; k++)
+        if (gids[k] < 0 || gids[k] >= c->E) {
+            set_err(err, HGX_ERR_KEY_NOT_FOUND, std::to_string(gids[k]) + ", Not Found");
+            return HGX_ERR_KEY_NOT_FOUND;
+        }
+    DeviceGuard dg(c);
+    const hgx::Engine::BodyOut out{sig_r, ntx, tx_off, tx_cap, tx_bytes, bytes_cap};
+    hgx::Engine::BodyFit fit = hgx::Engine::kBodyShort;
+    const hipError_t e = c->eng.bodies_gather(gids, nullptr, nullptr, count, out, n_tx, n_bytes, &fit);
+    return bodies_outcome(e, fit, err, who);
+}
+
+// The block's events from the host order arena (their gids go up at 8 bytes per event), then the
+// gather of hgx_get_event_bodies without the per-event columns.
+int32_t hgx_block_transactions(hgx_ctx* c, int32_t g, int64_t b, int64_t* tx_off, int64_t tx_cap, uint8_t* tx_bytes,
+                               int64_t bytes_cap, int64_t* n_tx, int64_t* n_bytes, hgx_error* err) {
+    const char* who = "hgx_block_transactions";
+    GraphState* s = graph(c, g);
+    if (!s || !n_tx || !n_bytes || tx_cap < 0 || bytes_cap < 0) {
+        set_err(err, HGX_ERR_INVALID, std::string(who) + ": bad arguments");
+        return HGX_ERR_INVALID;
+    }
+    if (bodies_gate(c, err, who)) return HGX_ERR_INVALID;
+    if (b < 0 || b >= (int64_t)s->blocks.size()) {
+        set_err(err, HGX_ERR_KEY_NOT_FOUND, std::to_string(b) + ", Not Found");
+        return HGX_ERR_KEY_NOT_FOUND;
+    }
+    const Block& blk = s->blocks[(size_t)b];
+    if (blk.first < 0) {
+        set_err(err, HGX_ERR_TOO_LATE, std::string(who) + ": block " + std::to_string(b) + ": events no longer resident");
+        return HGX_ERR_TOO_LATE;
+    }
+    std::vector<int64_t> gids((size_t)blk.nev);
+    walk_order(c, g, blk.first, blk.nev, [&](int64_t k, int64_t x) { gids[(size_t)k] = x; });
+    DeviceGuard dg(c);
+    const hgx::Engine::BodyOut out{nullptr, nullptr, tx_off, tx_cap, tx_bytes, bytes_cap};
+    hgx::Engine::BodyFit fit = hgx::Engine::kBodyShort;
+    const hipError_t e = c->eng.bodies_gather(gids.data(), nullptr, nullptr, blk.nev, out, n_tx, n_bytes, &fit);
+    if (e == hipSuccess && fit != hgx::Engine::kBodyTooLarge && *n_tx != blk.ntx) {
+        set_err(err, HGX_ERR_PANIC, std::string(who) + ": the store holds " + std::to_string(*n_tx) +
+                                        " transactions for block " + std::to_string(b) + ", the block " +
+                                        std::to_string(blk.ntx));
+        return HGX_ERR_PANIC;
+    }
+    return bodies_outcome(e, fit, err, who);
+}
+
+// Block.Hash of block b, computed on the device when the block was made on a keeping context
+int32_t hgx_get_block_hash(hgx_ctx* c, int32_t g, int64_t b, uint8_t* out32, hgx_error* err) {
+    const char* who = "hgx_get_block_hash";
+    GraphState* s = graph(c, g);
+    if (!s || !out32) {
+        set_err(err, HGX_ERR_INVALID, std::string(who) + ": bad arguments");
+        return HGX_ERR_INVALID;
+    }
+    if (c->eng.bodies_state == hgx::kBodiesOff || c->eng.bodies_state == hgx::kBodiesLost)
+        return bodies_gate(c, err, who);
+    if (b < 0 || b >= (int64_t)s->blocks.size() || !s->blocks[(size_t)b].has_hash) {
+        set_err(err, HGX_ERR_KEY_NOT_FOUND, std::to_string(b) + ", Not Found");
+        return HGX_ERR_KEY_NOT_FOUND;
+    }
+    std::memcpy(out32, s->blocks[(size_t)b].hash, 32);
+    return ok(err);
+}
+
+int32_t hgx_diff_wire_bodies(hgx_ctx* c, int32_t g, const int32_t* known, int64_t sync_limit, hgx_wire_out* out,
+                             hgx_wire_body_out* body, int64_t cap, int64_t* count, int64_t* n_tx, int64_t* n_bytes,
+                             int32_t* over_limit, hgx_error* err) {
+    const char* who = "hgx_diff_wire_bodies";
+    if (!c || !count || !n_tx || !n_bytes || (body && (body->tx_cap < 0 || body->bytes_cap < 0))) {
+        set_err(err, HGX_ERR_INVALID, std::string(who) + ": bad arguments");
+        return HGX_ERR_INVALID;
+    }
+    if (bodies_gate(c, err, who)) return HGX_ERR_INVALID;
+    hgx::Engine::DiffBodies db{};
+    if (body) db.out = hgx::Engine::BodyOut{body->sig_r, nullptr, body->tx_off, body->tx_cap, body->tx_bytes, body->bytes_cap};
+    int64_t total = 0;
+    int32_t over = 0;
+    const int32_t rc = diff_wire_impl(c, g, known, sync_limit, out, cap, &total, &over, err, who, &db);
+    if (rc != HGX_OK) return rc;
+    if (count) *count = total;
+    if (over_limit) *over_limit = over;
+    *n_tx = db.n_tx;
+    *n_bytes = db.n_bytes;
+    if (over || !db.ran) return ok(err);   // over the limit, or no row asked for: nothing gathered
+    return bodies_outcome(hipSuccess, db.fit, err, who);
 }
 
 // ReadWireInfo (hashgraph.go:569-614): the parents of a wire event resolved through

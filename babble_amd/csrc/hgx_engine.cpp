@@ -1,6 +1,7 @@
 // Engine host code: device allocation, per-call orchestration of the kernels,
 // D2H of the small per-round tables the Go-semantics bookkeeping needs.
 #include "hgx_engine.h"
+#include "hgx_bodystore.h"
 
 #include <algorithm>
 #include <array>
@@ -138,6 +139,7 @@ Engine::~Engine() {
     if (h_flag) (void)hipHostFree(h_flag);
     if (h_segc) (void)hipHostFree(h_segc);
     if (df_host) (void)hipHostFree(df_host);
+    if (b_host) (void)hipHostFree(b_host);
     if (pipe_thread.joinable()) pipe_thread.join();
     if (stream_p) {
         (void)hipStreamSynchronize(stream_p);
@@ -844,6 +846,7 @@ hipError_t Engine::clear() {
     laid_out = false;
     ids_known = true;
     pipe_ready = false;
+    HGX_TRY(bodies_reset());   // (nothing queued on a context that keeps no bodies)
     return hipStreamSynchronize(stream);
 }
 
@@ -1114,7 +1117,16 @@ hipError_t Engine::prune_stage(const std::vector<int32_t>& cut, int64_t n_kept, 
     pr_in.creator = a.st_creator; pr_in.index32 = a.st_index; pr_in.sp32 = a.st_sp; pr_in.op32 = a.st_op;
     pr_in.ts = a.st_ts; pr_in.hash = a.st_hash; pr_in.S = a.st_S; pr_in.ntx = a.st_ntx;
     pr_count = n_kept;
+    pr_old_gid = a.old_gid;
     return hipSuccess;
+}
+
+// A keeping context, between prune_stage and the commit: the kept events' bodies into new tables.
+// Nothing the context holds is changed, so a failure here leaves it whole.
+hipError_t Engine::prune_bodies(bool* too_large) {
+    *too_large = false;
+    if (pr_count < 0) return hipErrorInvalidValue;
+    return bodies_compact(pr_old_gid, pr_count, too_large);
 }
 
 // Commit: Reset with the new roots and Root.Others keys, then InsertEvent for the staged batch (the
@@ -1124,7 +1136,10 @@ hipError_t Engine::prune_to_frame(const std::vector<int32_t>& root_round, const 
     if (pr_count < 0) return hipErrorInvalidValue;
     const int64_t count = pr_count;
     pr_count = -1;
+    const bool lost = bodies_state == kBodiesLost;   // a prune is no hgx_clear: a lost store stays lost
     HGX_TRY(clear());
+    if (lost) bodies_state = kBodiesLost;
+    HGX_TRY(bodies_install());
     HGX_TRY(set_roots(root_round, y_ext));
     HGX_TRY(set_root_others(st.oth_key.data(), st.n_others));
     return insert(pr_in, count, out);
@@ -1135,7 +1150,7 @@ hipError_t Engine::prune_to_frame(const std::vector<int32_t>& root_round, const 
 // launch: known | root_index go up through the staged-copy path, three launches, and the header
 // (the device's total) with every requested column comes back in ONE copy, then one synchronise.
 hipError_t Engine::diff_wire(int graph, const int32_t* known, const int32_t* root_index, int64_t rows, int64_t expect,
-                             const DiffCols& out, int64_t* dev_total) {
+                             const DiffCols& out, int64_t* dev_total, DiffBodies* body) {
     *dev_total = expect;
     if (graph < 0 || graph >= G || rows < 0 || rows > expect || expect > E || (out.hash && !ids_known))
         return hipErrorInvalidValue;
@@ -1153,13 +1168,14 @@ hipError_t Engine::diff_wire(int graph, const int32_t* known, const int32_t* roo
     const size_t o_tab = take(2 * nz * 4), o_part = take(nb * 4), o_hdr = take(256);
     // the columns, widest first so that each stays aligned to its element (the 32-byte rows to 16)
     size_t col = o_hdr + 256;
-    auto column = [&](const void* want, size_t width) {
+    auto column = [&](bool want, size_t width) {
         if (!want) return (size_t)0;
         const size_t off = col;
         col += width * R;
         return off;
     };
-    const size_t c_hash = column(out.hash, 32), c_S = column(out.S, 32), c_gid = column(out.gid, 8),
+    const size_t c_hash = column(out.hash, 32), c_S = column(out.S, 32),
+                 c_gid = column(out.gid || body, 8),   // (the body gather's list is the gid column)
                  c_index = column(out.index, 8), c_spi = column(out.spi, 8), c_opi = column(out.opi, 8),
                  c_ts = column(out.ts, 8), c_creator = column(out.creator, 4), c_opc = column(out.opc, 4),
                  c_ntx = column(out.ntx, 4), c_nil = column(out.nil, 4), c_root = column(out.root, 1);
@@ -1199,7 +1215,15 @@ hipError_t Engine::diff_wire(int graph, const int32_t* known, const int32_t* roo
     uint32_t dt = 0;
     std::memcpy(&dt, df_host, 4);
     *dev_total = dt;
-    if ((int64_t)dt == expect) {   // (a mismatch is a bug the caller reports: nothing is handed out)
+    bool hand_out = (int64_t)dt == expect;   // (a mismatch is a bug the caller reports: nothing is handed out)
+    if (hand_out && body) {
+        // hgx_diff_wire_bodies: the selected gids are in the staging; their R and transactions follow, and
+        // the plain columns go out only when those fit
+        body->ran = true;
+        HGX_TRY(bodies_gather(nullptr, a.o_gid, nullptr, rows, body->out, &body->n_tx, &body->n_bytes, &body->fit));
+        hand_out = body->fit == kBodyFits;
+    }
+    if (hand_out) {
         auto give = [&](void* dst, size_t off, size_t width) {
             if (dst && off) std::memcpy(dst, df_host + (off - o_hdr), width * R);
         };

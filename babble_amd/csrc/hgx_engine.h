@@ -159,6 +159,58 @@ class Engine {
                                   const WireWindows& w, uint8_t* out_id32, int64_t* out_sp, int64_t* out_op,
                                   InsertOut& out);
     EvScratch* ev_scratch = nullptr;
+    // The resident body store (hgx_keep_bodies, hgx_bodystore.hip): R and the
+    // transaction bytes of every event, appended by insert_bodies_run behind each chunk's insert and
+    // read back by gid. bodies_state: hgx_bodystore.h's (off / complete / lost); the caller (finish_insert)
+    // marks the store lost when events arrived without their bodies (bodies_events != E).
+    struct BodyOut {   // host arrays, any may be null (capacities in transactions / bytes)
+        uint8_t* sig_r;
+        int32_t* ntx;
+        int64_t* tx_off;
+        int64_t tx_cap;
+        uint8_t* tx_bytes;
+        int64_t bytes_cap;
+    };
+    // a gather's outcome: the caller's capacities are short (the totals alone are reported), the arrays
+    // are written, or the list names 4 GiB or more (nothing was copied)
+    enum BodyFit { kBodyShort = 0, kBodyFits = 1, kBodyTooLarge = 2 };
+    struct BodyPlan {   // a measured gather: the list, its scanned counts (device scratch) and totals
+        int64_t m = 0, n_tx = 0, n_bytes = 0;
+        const int64_t* gids64 = nullptr;
+        const int32_t* gids32 = nullptr;
+        uint32_t *cnt_tx = nullptr, *cnt_by = nullptr;
+        bool too_large = false;
+    };
+    hipError_t bodies_keep(int64_t tx_hint, int64_t bytes_hint);
+    hipError_t bodies_reset();
+    hipError_t bodies_reserve(int64_t add_tx, int64_t add_bytes);
+    hipError_t bodies_append(const uint8_t* r, const int64_t* txi, const int64_t* off, const uint8_t* bytes, int64_t a,
+                             int64_t nt, int64_t nbytes);
+    hipError_t bodies_measure(const int64_t* gids_host, const int64_t* gids_dev64, const int32_t* gids_dev32, int64_t m,
+                              BodyPlan& plan);
+    hipError_t bodies_copy(const BodyPlan& plan, uint8_t* o_R, int32_t* o_ntx, int64_t* o_txi, int64_t* o_off,
+                           uint8_t* o_bytes);
+    hipError_t bodies_gather(const int64_t* gids_host, const int64_t* gids_dev64, const int32_t* gids_dev32, int64_t m,
+                             const BodyOut& out, int64_t* n_tx, int64_t* n_bytes, BodyFit* fit);
+    // hgx_prune_to_frame on a keeping context, behind prune_stage and before anything is dropped: the
+    // kept events' bodies gathered into new tables, which prune_to_frame puts in place. On a failure
+    // (hipErrorOutOfMemory; *too_large: the kept bodies reach 4 GiB) the context is as it was.
+    hipError_t prune_bodies(bool* too_large);
+    hipError_t bodies_compact(const int32_t* old_gid_dev, int64_t kept, bool* too_large);
+    // Block.Hash of the last find_order's new blocks (hgx_goenc_dev.hip): `count` blocks over the n_events
+    // newly ordered events, in the order's own sequence; rr / ntx / nil host arrays, out32 32 bytes per block.
+    // *too_large: the blocks' bytes or text reach 4 GiB, nothing was hashed. Changes nothing but scratch.
+    hipError_t order_block_hashes(int64_t n_events, const int64_t* rr, const int32_t* ntx, const int32_t* nil,
+                                  int64_t count, uint8_t* out32, bool* too_large);
+    hipError_t bodies_install();
+    int bodies_state = 0;
+    int64_t bodies_events = 0, bodies_tx = 0, bodies_bytes = 0;
+    DBuf<uint8_t> b_R, b_arena, b_work, b_out, b_new_arena, b_new_rows;
+    DBuf<int64_t> b_txi, b_off, b_new_off;
+    bool b_new_ready = false;
+    int64_t b_new_events = 0, b_new_tx = 0, b_new_bytes = 0;
+    uint8_t* b_host = nullptr;   // page-locked: a gather's result comes back in one copy
+    size_t b_host_cap = 0;
     // The roots' ids on the device: Root.X / Root.Y per chain and the Root.Others
     // pairs sorted by event id, the text of the parents that are in no id column. has_x / has_y: [C];
     // pairs: (event id, other-parent id) sorted by event id. root_ids_set = some id is installed (a
@@ -230,8 +282,16 @@ class Engine {
         int32_t *creator, *opc, *ntx, *nil;
         uint8_t *hash, *S, *root;
     };
+    // body (hgx_diff_wire_bodies, may be null): R and the transactions of the same rows from the body
+    // store, gathered behind the selection; then no column is written unless they fit body->out.
+    struct DiffBodies {
+        BodyOut out{};
+        int64_t n_tx = 0, n_bytes = 0;
+        BodyFit fit = kBodyShort;
+        bool ran = false;
+    };
     hipError_t diff_wire(int graph, const int32_t* known, const int32_t* root_index, int64_t rows, int64_t expect,
-                         const DiffCols& out, int64_t* dev_total);
+                         const DiffCols& out, int64_t* dev_total, DiffBodies* body = nullptr);
     // chain lengths at the last DivideRounds (events past them have no round yet)
     int32_t len_div(int chain) const { return laid_out && chain < (int)h_len_div.size() ? h_len_div[(size_t)chain] : 0; }
     // per-event columns (gid order) for the host-side getters
@@ -458,6 +518,7 @@ class Engine {
     DBuf<uint8_t> pr_buf;
     InsertIn pr_in{};
     int64_t pr_count = -1;   // events staged by prune_stage (-1: none)
+    const int32_t* pr_old_gid = nullptr;   // ... their old gids (in pr_buf)
     // hgx_diff_wire: known | root_index, the per-2 048-gid partials, then a 256-byte header (the
     // device's total) and the output columns, 121 bytes per returned row; the header and the
     // columns come back in one copy into df_host (page-locked). Both grown on demand.

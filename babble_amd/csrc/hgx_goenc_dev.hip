@@ -24,6 +24,7 @@
 
 #include "hgx.h"
 #include "hgx_bodies.h"
+#include "hgx_bodystore.h"
 #include "hgx_engine.h"
 #include "hgx_sha256_dev.h"
 
@@ -460,6 +461,7 @@ struct EvScratch {
     // hgx_insert_wire_bodies: lo[n] | woff[n], then the window (4 bytes per slot); the
     // table goes up from a page-locked copy
     DevMem wire;
+    DevMem blk_meta, blk_sz, blk_text, blk_out, blk_in;   // the block encoder (block_hashes_run)
     int32_t* h_wtab = nullptr;
     size_t h_wtab_cap = 0;
     ~EvScratch() {
@@ -504,7 +506,9 @@ struct EvScratch {
         size_t o[19], total = 0;
         for (int i = 0; i < 19; i++) {
             o[i] = total;
-            total += up256(bytes[i] + 16);   // (16 spare bytes: the hash reader's aligned loads)
+            // 16 spare bytes behind every column: the hash reader's aligned loads, and for tx_bytes
+            // (o[10]) the shifted dword reads of k_body_append's copy_bytes, up to 7 bytes past the end
+            total += up256(bytes[i] + 16);
         }
         if (h_cap < total) {
             if (h) (void)hipHostFree(h);
@@ -631,6 +635,17 @@ hipError_t Engine::insert_bodies_run(const BodiesIn& ev, const std::vector<int64
         int64_t bound = 0;
         const int64_t hi = bodies_chunk_end(ev, txi, done, count, &bound);
         const int64_t m = hi - done;
+        // a keeping context: room for the whole chunk before any of it is inserted
+        const bool keep = bodies_state == kBodiesComplete && bodies_events == E;
+        const int64_t t_lo = txi[(size_t)done];
+        if (keep && bodies_reserve(txi[(size_t)hi] - t_lo, ev.tx_off[txi[(size_t)hi]] - ev.tx_off[t_lo]) != hipSuccess) {
+            InsertOut co;   // the earlier chunks stay inserted: their state, and the store's own failure code
+            HGX_TRY(insert_verified(InsertIn{}, nullptr, nullptr, 0, co));
+            out = std::move(co);
+            out.accepted = done;
+            out.code = INS_BODY_CAPACITY;
+            break;
+        }
         HGX_TRY(sc.stage(ev, txi, done, hi, pk_keys.p, nullptr, C, nullptr, nullptr, true, E, n, stream, rt.has_x, op_id32));
         if (wire && wire->win)   // window descriptors -> gids, before the encoder reads the parent columns
             launch_wire_resolve(stream, m, const_cast<int64_t*>(sc.cols.sp), const_cast<int64_t*>(sc.cols.op), wire->win,
@@ -653,6 +668,11 @@ hipError_t Engine::insert_bodies_run(const BodiesIn& ev, const std::vector<int64
         in.ts = sc.cols.ts; in.hash = sc.d_ids; in.S = sc.cols.s; in.ntx = sc.cols.ntx; in.nil = nullptr;
         InsertOut co;
         HGX_TRY(insert_verified(in, sc.d_dig, sc.cols.r, m, co));
+        if (keep && co.accepted > 0) {   // the accepted prefix's R rows, slots, offsets and bytes (one launch)
+            const int64_t t_hi = txi[(size_t)(done + co.accepted)];
+            HGX_TRY(bodies_append(sc.cols.r, sc.cols.txi, sc.cols.tx_off, sc.cols.tx_bytes, co.accepted, t_hi - t_lo,
+                                  ev.tx_off[t_hi] - ev.tx_off[t_lo]));
+        }
         if (wire && wire->win && co.code) {
             // a window slot nobody filled made this event fail its checks: that bug is the finding
             int64_t par[2] = {0, 0};
@@ -678,6 +698,224 @@ hipError_t Engine::insert_bodies_run(const BodiesIn& ev, const std::vector<int64
         if (out.code) break;
     }
     return hipSuccess;
+}
+
+
+// ---- Block.Hash (block.go:44-53) for a batch of blocks -----------------------
+// The block text is hgx_block_hash's: {"RoundReceived":N,"Transactions":T}\n with T = null for a nil
+// list without transactions, else [ "<std base64, padded>", ... ]. The texts are laid out as elements,
+// block b's head at element tx0[b] + b and its transactions behind it: the head carries everything up
+// to and including '[' (or the whole rest of a block without transactions), a transaction its quoted
+// base64 and the comma, or "]}\n" behind the block's last one. One more element of size 0 ends the
+// array, so the scan's value at a block's head is where its text starts.
+struct BlkArgs {
+    int64_t count, T;
+    const int64_t* rr;       // [count]
+    const int64_t* tx0;      // [count + 1] first transaction of each block
+    const int32_t* nil;      // [count]
+    const int32_t* tx_blk;   // [T] the block of each transaction
+    const int64_t* off;      // [T + 1] offsets into bytes
+    const uint8_t* bytes;
+    uint32_t* sz;            // [T + count + 1] element sizes, then their exclusive scan
+    int64_t* starts;         // [count + 1] text start of each block
+};
+
+__device__ __forceinline__ int blk_decimal(int64_t v, char* buf) {   // digits (and '-') of v, returns the length
+    char tmp[20];
+    int n = 0;
+    const bool neg = v < 0;
+    do {
+        const int d = (int)(v % 10);
+        tmp[n++] = (char)('0' + (d < 0 ? -d : d));
+        v /= 10;
+    } while (v != 0);
+    int len = 0;
+    if (neg) buf[len++] = '-';
+    while (n > 0) buf[len++] = tmp[--n];
+    return len;
+}
+
+__device__ __forceinline__ int blk_decimal_len(int64_t v) {
+    int len = v < 0 ? 1 : 0;
+    do {
+        len++;
+        v /= 10;
+    } while (v != 0);
+    return len;
+}
+
+__global__ void __launch_bounds__(256) k_blk_size(BlkArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < a.count) {
+        const int64_t nt = a.tx0[i + 1] - a.tx0[i];
+        uint32_t s = 17 + (uint32_t)blk_decimal_len(a.rr[i]) + 16;
+        s += nt > 0 ? 1u : (a.nil[i] ? 6u : 4u);   // "["  |  "null}\n"  |  "[]}\n"
+        a.sz[a.tx0[i] + i] = s;
+    }
+    if (i < a.T) {
+        const int32_t b = a.tx_blk[i];
+        const int64_t l = a.off[i + 1] - a.off[i];
+        a.sz[i + b + 1] = (uint32_t)(4 * ((l + 2) / 3) + 2 + (i + 1 == a.tx0[b + 1] ? 3 : 1));
+    }
+    if (i == 0) a.sz[a.T + a.count] = 0;
+}
+
+__global__ void __launch_bounds__(256) k_blk_starts(BlkArgs a) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b <= a.count) a.starts[b] = (int64_t)a.sz[a.tx0[b] + b];
+}
+
+// one thread per block of [b_lo, b_hi): the head (and the tail of a block without transactions)
+__global__ void __launch_bounds__(256) k_blk_heads(BlkArgs a, int64_t b_lo, int64_t b_hi, int64_t base,
+                                                   uint8_t* __restrict__ text) {
+    const int64_t b = b_lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= b_hi) return;
+    uint8_t* p = text + ((int64_t)a.sz[a.tx0[b] + b] - base);
+    const char h1[] = "{\"RoundReceived\":", h2[] = ",\"Transactions\":";
+    for (int k = 0; k < 17; k++) *p++ = (uint8_t)h1[k];
+    char dec[20];
+    const int nd = blk_decimal(a.rr[b], dec);
+    for (int k = 0; k < nd; k++) *p++ = (uint8_t)dec[k];
+    for (int k = 0; k < 16; k++) *p++ = (uint8_t)h2[k];
+    if (a.tx0[b + 1] > a.tx0[b]) {
+        *p = '[';
+    } else if (a.nil[b]) {
+        const char t[] = "null}\n";
+        for (int k = 0; k < 6; k++) p[k] = (uint8_t)t[k];
+    } else {
+        const char t[] = "[]}\n";
+        for (int k = 0; k < 4; k++) p[k] = (uint8_t)t[k];
+    }
+}
+
+// a wave per transaction of [t_lo, t_hi), its lanes strided over the 3-byte groups
+__global__ void __launch_bounds__(256) k_blk_txs(BlkArgs a, int64_t t_lo, int64_t t_hi, int64_t base,
+                                                 uint8_t* __restrict__ text) {
+    const int64_t j = t_lo + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= t_hi) return;
+    const int lane = (int)(threadIdx.x & 63);
+    const int32_t b = a.tx_blk[j];
+    const int64_t l = a.off[j + 1] - a.off[j], ng = (l + 2) / 3;
+    const uint8_t* src = a.bytes + a.off[j];
+    uint8_t* p = text + ((int64_t)a.sz[j + b + 1] - base);
+    for (int64_t g = lane; g < ng; g += 64) {
+        const int64_t at = 3 * g;
+        const int have = (int)(l - at < 3 ? l - at : 3);
+        const uint32_t v = (uint32_t)src[at] << 16 | (have > 1 ? (uint32_t)src[at + 1] << 8 : 0u) |
+                           (have > 2 ? (uint32_t)src[at + 2] : 0u);
+        uint8_t* q = p + 1 + 4 * g;
+        q[0] = (uint8_t)b64_char(v >> 18);
+        q[1] = (uint8_t)b64_char((v >> 12) & 63);
+        q[2] = have > 1 ? (uint8_t)b64_char((v >> 6) & 63) : (uint8_t)'=';
+        q[3] = have > 2 ? (uint8_t)b64_char(v & 63) : (uint8_t)'=';
+    }
+    if (lane == 0) {
+        p[0] = '"';
+        uint8_t* q = p + 1 + 4 * ng;
+        q[0] = '"';
+        if (j + 1 == a.tx0[b + 1]) {
+            q[1] = ']'; q[2] = '}'; q[3] = '\n';
+        } else {
+            q[1] = ',';
+        }
+    }
+}
+
+// Block.Hash of blocks [b_lo, b_hi): one lane per text
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
+k_blk_digest(BlkArgs a, int64_t b_lo, int64_t b_hi, int64_t base, const uint8_t* __restrict__ text,
+             uint8_t* __restrict__ out) {
+    const int64_t b = b_lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= b_hi) return;
+    sha256_message<false>(text, a.starts[b] - base, a.starts[b + 1] - a.starts[b], 0, (uint32_t*)(out + 32 * b));
+}
+
+constexpr int64_t kBlkTextGroup = (int64_t)32 << 20;   // text scratch per group of blocks (§3.10's bound)
+
+// The hashes of `count` blocks whose transactions are on the device (d_off [T + 1] offsets from any
+// base into d_bytes, T = the sum of ntx): sizing pass, scan, then per group of at most kBlkTextGroup of
+// text (a single larger block raises the bound to its size) write pass and SHA-256; the hashes come
+// back in one copy. rr / ntx / nil are host arrays.
+static hipError_t block_hashes_run(hipStream_t s, EvScratch& sc, const int64_t* rr, const int32_t* ntx, const int32_t* nil,
+                                   int64_t count, const int64_t* d_off, const uint8_t* d_bytes, uint8_t* out32_host) {
+    if (count <= 0) return hipSuccess;
+    const size_t B = (size_t)count;
+    std::vector<int64_t> tx0(B + 1, 0);
+    for (size_t b = 0; b < B; b++) tx0[b + 1] = tx0[b] + (ntx[b] > 0 ? ntx[b] : 0);
+    const size_t T = (size_t)tx0[B];
+    if (T + B + 1 >= ((size_t)1 << 31)) return hipErrorInvalidValue;
+    std::vector<int32_t> tx_blk(T);
+    for (size_t b = 0; b < B; b++)
+        for (int64_t j = tx0[b]; j < tx0[b + 1]; j++) tx_blk[(size_t)j] = (int32_t)b;
+    const size_t o_rr = 0, o_tx0 = up256(8 * B), o_nil = o_tx0 + up256(8 * (B + 1)), o_blk = o_nil + up256(4 * B),
+                 o_st = o_blk + up256(4 * T), meta = o_st + up256(8 * (B + 1));
+    HGX_TRY(sc.blk_meta.need(meta));
+    const size_t ne = T + B + 1, nparts = (ne + 2047) / 2048 + 1;
+    HGX_TRY(sc.blk_sz.need(up256(4 * ne) + 4 * nparts));
+    HGX_TRY(sc.blk_out.need(32 * B));
+    uint8_t* m = sc.blk_meta.p;
+    HGX_TRY(hipMemcpyAsync(m + o_rr, rr, 8 * B, hipMemcpyHostToDevice, s));
+    HGX_TRY(hipMemcpyAsync(m + o_tx0, tx0.data(), 8 * (B + 1), hipMemcpyHostToDevice, s));
+    HGX_TRY(hipMemcpyAsync(m + o_nil, nil, 4 * B, hipMemcpyHostToDevice, s));
+    if (T) HGX_TRY(hipMemcpyAsync(m + o_blk, tx_blk.data(), 4 * T, hipMemcpyHostToDevice, s));
+    BlkArgs a{count, (int64_t)T, (const int64_t*)(m + o_rr), (const int64_t*)(m + o_tx0), (const int32_t*)(m + o_nil),
+              (const int32_t*)(m + o_blk), d_off, d_bytes, (uint32_t*)sc.blk_sz.p, (int64_t*)(m + o_st)};
+    const size_t work = std::max(B, T);
+    hipLaunchKernelGGL(k_blk_size, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, a);
+    launch_scan_u32(s, a.sz, (int64_t)ne, (uint32_t*)(sc.blk_sz.p + up256(4 * ne)));
+    hipLaunchKernelGGL(k_blk_starts, dim3((unsigned)((B + 1 + 255) / 256)), dim3(256), 0, s, a);
+    HGX_TRY(hipGetLastError());
+    std::vector<int64_t> starts(B + 1);
+    HGX_TRY(hipMemcpyAsync(starts.data(), a.starts, 8 * (B + 1), hipMemcpyDeviceToHost, s));
+    HGX_TRY(hipStreamSynchronize(s));   // (also: the host vectors above have been read)
+    // the positions are 32-bit: the callers refused a batch whose text could reach 4 GiB
+    // (block_text_fits, on the host in 64 bits), so the device's total is the true one
+    if (!block_text_fits(starts[B])) return hipErrorInvalidValue;
+    for (size_t b = 0; b < B; b++)
+        if (starts[b + 1] < starts[b]) return hipErrorInvalidValue;
+    for (int64_t lo = 0; lo < count;) {
+        int64_t hi = lo + 1;
+        while (hi < count && starts[(size_t)hi + 1] - starts[(size_t)lo] <= kBlkTextGroup) hi++;
+        const int64_t base = starts[(size_t)lo], bytes = starts[(size_t)hi] - base;
+        HGX_TRY(sc.blk_text.need((size_t)bytes + 64));
+        hipLaunchKernelGGL(k_blk_heads, dim3((unsigned)((hi - lo + 255) / 256)), dim3(256), 0, s, a, lo, hi, base,
+                           sc.blk_text.p);
+        const int64_t t_lo = tx0[(size_t)lo], t_hi = tx0[(size_t)hi];
+        if (t_hi > t_lo)
+            hipLaunchKernelGGL(k_blk_txs, dim3((unsigned)((t_hi - t_lo + 3) / 4)), dim3(256), 0, s, a, t_lo, t_hi, base,
+                               sc.blk_text.p);
+        hipLaunchKernelGGL(k_blk_digest, dim3((unsigned)((hi - lo + 255) / 256)), dim3(256), 0, s, a, lo, hi, base,
+                           (const uint8_t*)sc.blk_text.p, sc.blk_out.p);
+        HGX_TRY(hipGetLastError());
+        lo = hi;
+    }
+    HGX_TRY(hipMemcpyAsync(out32_host, sc.blk_out.p, 32 * B, hipMemcpyDeviceToHost, s));
+    return hipStreamSynchronize(s);
+}
+
+// hgx_find_order on a keeping context: the call's new blocks are contiguous ranges of the device order
+// (graph-major, rr ascending). Their transactions are gathered from the body store straight from the
+// order's gids (device to device), encoded and hashed; 32 bytes per block come back.
+hipError_t Engine::order_block_hashes(int64_t n_events, const int64_t* rr, const int32_t* ntx, const int32_t* nil,
+                                      int64_t count, uint8_t* out32, bool* too_large) {
+    *too_large = false;
+    if (bodies_state != kBodiesComplete || count <= 0) return hipErrorInvalidValue;
+    if (!ev_scratch) ev_scratch = new EvScratch();
+    BodyPlan plan;
+    HGX_TRY(bodies_measure(nullptr, nullptr, order_gid.p, n_events, plan));
+    int64_t want = 0;
+    for (int64_t b = 0; b < count; b++) want += ntx[b];
+    if (plan.too_large || !block_text_fits(block_text_bound(count, plan.n_tx, plan.n_bytes))) {
+        *too_large = true;
+        return hipSuccess;
+    }
+    if (plan.n_tx != want) return hipErrorInvalidValue;   // (the store and the blocks disagree: a bug)
+    const size_t o_by = up256(8 * ((size_t)plan.n_tx + 1));
+    HGX_TRY(ev_scratch->blk_in.need(o_by + up256((size_t)plan.n_bytes + 16)));
+    int64_t* d_off = (int64_t*)ev_scratch->blk_in.p;
+    if (n_events > 0) HGX_TRY(bodies_copy(plan, nullptr, nullptr, nullptr, d_off, ev_scratch->blk_in.p + o_by));
+    else HGX_TRY(hipMemsetAsync(d_off, 0, 8, stream));
+    return block_hashes_run(stream, *ev_scratch, rr, ntx, nil, count, d_off, ev_scratch->blk_in.p + o_by, out32);
 }
 
 }  // namespace hgx
@@ -768,5 +1006,69 @@ extern "C" int32_t hgx_event_json_batch(int32_t device, const hgx_event_bodies* 
         return HGX_ERR_DEVICE;
     }
     if (!fits) return invalid(err, "hgx_event_json_batch: out_cap is smaller than the batch's text");
+    return HGX_OK;
+}
+
+extern "C" int32_t hgx_block_hash_batch(int32_t device, const int64_t* round_received, const int32_t* ntx,
+                                        const int32_t* tx_nil, const int64_t* tx_off, const uint8_t* tx_bytes,
+                                        int64_t count, uint8_t* out32, hgx_error* err) {
+    set_err(err, HGX_OK, "");
+    if (count < 0 || (count > 0 && (!round_received || !ntx || !tx_nil || !out32)))
+        return invalid(err, "hgx_block_hash_batch: bad arguments");
+    int64_t T = 0;
+    for (int64_t b = 0; b < count; b++) {
+        if (ntx[b] < 0) return invalid(err, "hgx_block_hash_batch: negative ntx");
+        T += ntx[b];
+    }
+    if (T > 0 && !tx_off) return invalid(err, "hgx_block_hash_batch: null tx_off");
+    for (int64_t j = 0; j < T; j++)
+        if (tx_off[j + 1] < tx_off[j]) return invalid(err, "hgx_block_hash_batch: tx_off decreases");
+    const int64_t nbytes = T > 0 ? tx_off[T] - tx_off[0] : 0;
+    if (nbytes > 0 && !tx_bytes) return invalid(err, "hgx_block_hash_batch: null tx_bytes");
+    int64_t text = 0;   // the encoder's positions are 32-bit: the batch's text, summed here in 64 bits
+    for (int64_t b = 0, t = 0; b < count && hgx::block_text_fits(text); t += ntx[b], b++)
+        text += hgx::block_text_len(round_received[b], ntx[b], tx_nil[b] != 0, tx_off ? tx_off + t : nullptr);
+    if (!hgx::block_text_fits(text)) {
+        set_err(err, HGX_ERR_CAPACITY, "hgx_block_hash_batch: the blocks' text reaches 4 GiB (hash fewer blocks per call)");
+        return HGX_ERR_CAPACITY;
+    }
+    if (count == 0) return HGX_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        set_err(err, HGX_ERR_DEVICE, "no HIP device available (libhgx has no CPU fallback)");
+        return HGX_ERR_DEVICE;
+    }
+    hipDeviceProp_t prop;
+    if (device < 0 || device >= ndev || hipGetDeviceProperties(&prop, device) != hipSuccess ||
+        std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+        set_err(err, HGX_ERR_DEVICE, "libhgx is built for gfx950 (MI355X) only");
+        return HGX_ERR_DEVICE;
+    }
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    (void)hipSetDevice(device);
+    hipStream_t s = nullptr;
+    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    {
+        hgx::EvScratch sc;
+        const size_t o_by = hgx::up256(8 * ((size_t)T + 1));
+        if (e == hipSuccess) e = sc.blk_in.need(o_by + hgx::up256((size_t)nbytes + 16));
+        const int64_t zero = 0;
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(sc.blk_in.p, T > 0 ? tx_off : &zero, 8 * ((size_t)T + 1), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess && nbytes > 0)
+            e = hipMemcpyAsync(sc.blk_in.p + o_by, tx_bytes + (T > 0 ? tx_off[0] : 0), (size_t)nbytes, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        // (the offsets keep the caller's base: the bytes are addressed from it)
+        if (e == hipSuccess)
+            e = hgx::block_hashes_run(s, sc, round_received, ntx, tx_nil, count, (const int64_t*)sc.blk_in.p,
+                                      sc.blk_in.p + o_by - (T > 0 ? tx_off[0] : 0), out32);
+    }
+    if (s) (void)hipStreamDestroy(s);
+    (void)hipSetDevice(prev);
+    if (e != hipSuccess) {
+        set_err(err, HGX_ERR_DEVICE, hipGetErrorString(e));
+        return HGX_ERR_DEVICE;
+    }
     return HGX_OK;
 }

@@ -102,7 +102,8 @@ enum InsertCode {
     INS_OK = 0, INS_KEY_NOT_FOUND = 1, INS_SELF_PARENT = 2, INS_OTHER_PARENT = 3, INS_CAPACITY = 4,
     INS_PASSED_INDEX = 5, INS_SKIPPED_INDEX = 6, INS_INDEX_RANGE = 7,
     INS_BAD_SIG = 8, INS_BAD_KEY = 9,  // Event.Verify: invalid signature / creator key not a P-256 point
-    INS_WIRE_HOLE = 10                 // hgx_insert_wire_bodies: a parent's window slot was never filled (a bug)
+    INS_WIRE_HOLE = 10,                // hgx_insert_wire_bodies: a parent's window slot was never filled (a bug)
+    INS_BODY_CAPACITY = 11             // a keeping context (hgx_keep_bodies): the body store could not grow for a chunk
 };
 constexpr int64_t kWireHoleParent = -2;   // HGX_UNKNOWN_PARENT (include/hgx.h)
 

@@ -188,6 +188,25 @@ def event_json_batch(cols: dict, keys65, sp_id32, op_id32, device: int = 0, out_
     return out[:int(offsets[m])], offsets
 
 
+def block_hash_batch(blocks, device: int = 0) -> List[bytes]:
+    """Block.Hash of every (round_received, txs, tx_nil) of `blocks` on the device (hgx_block_hash_batch, the
+    block encoder alone): txs a list of byte strings; null is printed for tx_nil and no transactions."""
+    blocks = list(blocks)
+    rr = np.asarray([b[0] for b in blocks], np.int64)
+    ntx = np.asarray([len(b[1]) for b in blocks], np.int32)
+    nil = np.asarray([1 if b[2] else 0 for b in blocks], np.int32)
+    flat = [t for b in blocks for t in b[1]]
+    off = np.zeros(len(flat) + 1, np.int64)
+    np.cumsum([len(t) for t in flat], out=off[1:])
+    by = np.frombuffer(b"".join(flat) + b"\0", np.uint8)
+    out, err = np.zeros((max(len(blocks), 1), 32), np.uint8), hgx_error()
+    rc = _lib.lib().hgx_block_hash_batch(device, ptr(rr) if len(blocks) else None, ptr(ntx) if len(blocks) else None,
+                                         ptr(nil) if len(blocks) else None, ptr(off), ptr(by), len(blocks), ptr(out),
+                                         C.byref(err))
+    _lib.check(rc, err)
+    return [out[k].tobytes() for k in range(len(blocks))]
+
+
 def batch_levels(sp, op, base: int = 0):
     """Each event's depth inside a batch whose first event gets gid `base` (hgx_batch_levels, host
     only): returns (level [count] int32, number of levels)."""
@@ -757,6 +776,111 @@ class Hashgraph:
             _lib.check(rc, err)
         m = 0 if over.value else min(rows, cnt.value)
         return {nm: a[:m] for nm, a in cols.items()}, cnt.value, bool(over.value)
+
+    # ------------------------------------------------------------------ the resident body store
+    def KeepBodies(self, tx_hint: int = 0, bytes_hint: int = 0):
+        """hgx_keep_bodies: from here on the body paths keep every accepted event's R and transaction
+        bytes on the device (a context with no events only). The hints are a first reservation."""
+        err = hgx_error()
+        _lib.check(self.L.hgx_keep_bodies(self.ctx, tx_hint, bytes_hint, C.byref(err)), err)
+
+    def BodiesState(self) -> dict:
+        """hgx_bodies_state: state 0 off / 1 complete / 2 lost, and the events, transactions and bytes held."""
+        ne, nt, nb = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        st = self.L.hgx_bodies_state(self.ctx, C.byref(ne), C.byref(nt), C.byref(nb))
+        return dict(state=int(st), events=ne.value, tx=nt.value, bytes=nb.value)
+
+    @staticmethod
+    def _sized(call):
+        """call(tx_off, tx_cap, tx_bytes, bytes_cap, n_tx, n_bytes) -> (rc, err): the sizing call with
+        NULL arrays, then the call with arrays of exactly that size. Returns (tx_off, tx_bytes)."""
+        nt, nb = C.c_int64(0), C.c_int64(0)
+        rc, err = call(None, 0, None, 0, nt, nb)
+        if rc not in (0, 103):   # HGX_ERR_CAPACITY: the totals are set
+            _lib.check(rc, err)
+        off, by = np.zeros(nt.value + 1, np.int64), np.zeros(max(nb.value, 1), np.uint8)
+        rc, err = call(off, nt.value, by, nb.value, nt, nb)
+        _lib.check(rc, err)
+        return off, by[:nb.value]
+
+    def EventBodies(self, gids) -> dict:
+        """hgx_get_event_bodies: R and the transactions of the events `gids` (any order, repeats allowed)
+        from the body store, as hgx_event_bodies' columns in list order: sig_r [m, 32], ntx [m] (-1 =
+        nil), tx_off [n_tx + 1] from 0, tx_bytes."""
+        gids = np.ascontiguousarray(gids, np.int64)
+        m = len(gids)
+        r, ntx = np.zeros((max(m, 1), 32), np.uint8), np.zeros(max(m, 1), np.int32)
+
+        def call(off, tcap, by, bcap, nt, nb):
+            err = hgx_error()
+            rc = self.L.hgx_get_event_bodies(self.ctx, ptr(gids) if m else None, m, ptr(r), ptr(ntx),
+                                             ptr(off) if off is not None else None, tcap,
+                                             ptr(by) if by is not None else None, bcap, C.byref(nt), C.byref(nb),
+                                             C.byref(err))
+            return rc, err
+
+        off, by = self._sized(call)
+        return dict(sig_r=r[:m], ntx=ntx[:m], tx_off=off, tx_bytes=by)
+
+    def BlockTransactions(self, b: int, graph: int = 0) -> List[bytes]:
+        """hgx_block_transactions: Block.Transactions of block b from the body store, in consensus order."""
+        def call(off, tcap, by, bcap, nt, nb):
+            err = hgx_error()
+            rc = self.L.hgx_block_transactions(self.ctx, graph, b, ptr(off) if off is not None else None, tcap,
+                                               ptr(by) if by is not None else None, bcap, C.byref(nt), C.byref(nb),
+                                               C.byref(err))
+            return rc, err
+
+        off, by = self._sized(call)
+        raw = by.tobytes()
+        return [raw[int(off[j]):int(off[j + 1])] for j in range(len(off) - 1)]
+
+    def BlockHash(self, b: int, graph: int = 0) -> bytes:
+        """hgx_get_block_hash: Block.Hash of block b, computed on the device when the block was made."""
+        out, err = np.zeros(32, np.uint8), hgx_error()
+        _lib.check(self.L.hgx_get_block_hash(self.ctx, graph, b, ptr(out), C.byref(err)), err)
+        return out.tobytes()
+
+    def DiffWireBodies(self, known, sync_limit: int = -1, graph: int = 0, cap: Optional[int] = None):
+        """A complete SyncResponse (hgx_diff_wire_bodies): DiffWire's columns plus sig_r, tx_off and
+        tx_bytes of the same rows from the body store. Returns (cols, count, over_limit); with
+        ntx = where(tx_nil, -1, ntx) the columns are insert_wire_bodies' on the peer. cap=None sizes by
+        the count."""
+        known = np.ascontiguousarray(known, np.int32)
+        if known.shape != (self.n,):
+            raise ValueError(f"known must have {self.n} entries")
+        spec = {nm: (dt, shp) for nm, dt, shp in _lib.WIRE_OUT_COLUMNS}
+        cnt, over, nt, nb = C.c_int64(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+
+        def call(cols, rows, body):
+            out, err = _lib.hgx_wire_out(**{nm: ptr(a) for nm, a in cols.items()}), hgx_error()
+            rc = self.L.hgx_diff_wire_bodies(self.ctx, graph, ptr(known), sync_limit, C.byref(out),
+                                             C.byref(body) if body is not None else None, rows, C.byref(cnt),
+                                             C.byref(nt), C.byref(nb), C.byref(over), C.byref(err))
+            return rc, err
+
+        def alloc(rows):
+            return {nm: np.zeros((max(rows, 1),) + shp, dt) for nm, (dt, shp) in spec.items()}
+
+        if cap is None:   # the row count first
+            rc, err = call(alloc(0), 0, None)
+            _lib.check(rc, err)
+        rows = cnt.value if cap is None else int(cap)
+        cols = alloc(rows)
+        if over.value and cap is None:
+            return {nm: a[:0] for nm, a in cols.items()}, cnt.value, True
+        rc, err = call(cols, rows, None)   # the rows' totals (no array is written unless they are zero)
+        if rc not in (0, 103):
+            _lib.check(rc, err)
+        r = np.zeros((max(rows, 1), 32), np.uint8)
+        off, by = np.zeros(nt.value + 1, np.int64), np.zeros(max(nb.value, 1), np.uint8)
+        body = _lib.hgx_wire_body_out(ptr(r), ptr(off), nt.value, ptr(by), nb.value)
+        rc, err = call(cols, rows, body)
+        _lib.check(rc, err)
+        m = 0 if over.value else min(rows, cnt.value)
+        res = {nm: a[:m] for nm, a in cols.items()}
+        res.update(sig_r=r[:m], tx_off=off, tx_bytes=by[:nb.value])
+        return res, cnt.value, bool(over.value)
 
     def ReadWireInfo(self, creator: int, sp_index: int, op_creator: int, op_index: int):
         sp, op, err = C.c_int64(), C.c_int64(), hgx_error()

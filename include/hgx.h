@@ -38,7 +38,9 @@ extern "C" {
 
 #define HGX_ABI_VERSION 6   /* (still 6 with hgx_insert_event_bodies(_ext), hgx_set_root_ids, hgx_event_json_batch and hgx_batch_levels,
                                  with hgx_prune_to_frame, hgx_get_root_ids and hgx_get_root_others, with hgx_diff_wire, and
-                                 with hgx_insert_wire_bodies:
+                                 with hgx_insert_wire_bodies, and with hgx_keep_bodies and its consumers
+                                 (hgx_get_event_bodies, hgx_block_transactions, hgx_get_block_hash,
+                                 hgx_block_hash_batch, hgx_diff_wire_bodies):
                                  purely additive, no existing entry or structure changed)
                               6: hgx_host_alloc / hgx_host_free (page-locked caller buffers);
                               5: hgx_events_packed (hgx_insert_events_packed, hgx_insert_and_run_packed,
@@ -557,7 +559,8 @@ int32_t hgx_participant_event(hgx_ctx* ctx, int32_t participant, int64_t index, 
  * (the genesis Root: Index = Round = -1, or the one hgx_reset installed) */
 int32_t hgx_get_root(hgx_ctx* ctx, int32_t participant, int64_t* x, int64_t* y, int32_t* index, int32_t* round,
                      hgx_error* err);
-/* GetEvent (inmem_store.go:48-55): the DAG fields of an inserted event (bodies stay with the caller) */
+/* GetEvent (inmem_store.go:48-55): the DAG fields of an inserted event (bodies stay with the caller, or with
+ * the context after hgx_keep_bodies: hgx_get_event_bodies) */
 int32_t hgx_get_event(hgx_ctx* ctx, int64_t gid, int32_t* creator, int64_t* index, int64_t* self_parent,
                       int64_t* other_parent, int64_t* timestamp_ns, int32_t* ntx, int32_t* tx_nil, hgx_error* err);
 /* SetWireInfo (hashgraph.go:532-567) of events [first, first+count): self-parent Index
@@ -608,7 +611,8 @@ typedef struct {
  * that are not written; *over_limit = 0 (over_limit may be NULL). creator_id and other_parent_creator
  * are ids within the graph, 0..n-1, as a WireBody carries them, so the columns are directly the
  * hgx_wire_events of hgx_insert_wire_events on the peer. R and the transaction bytes stay with the
- * caller's body store, keyed by gid. Works on batched (G > 1) and row-sharded contexts. The call
+ * caller's body store, keyed by gid; on a context that keeps them (hgx_keep_bodies) hgx_diff_wire_bodies
+ * returns them with the rows. Works on batched (G > 1) and row-sharded contexts. The call
  * changes no context state apart from scratch buffers (121 bytes per returned row, and one word per
  * 2 048 resident events), and neither builds nor drops the host mirror behind the other store views.
  * HGX_ERR_INVALID "<reason>", nothing written: NULL ctx, known, out or count; graph outside the
@@ -616,6 +620,84 @@ typedef struct {
  * (hgx_events32 / packed inserts: the other columns still work there). */
 int32_t hgx_diff_wire(hgx_ctx* ctx, int32_t graph, const int32_t* known, int64_t sync_limit,
                       hgx_wire_out* out, int64_t cap, int64_t* count, int32_t* over_limit, hgx_error* err);
+
+/* ---- the resident body store ---------------------------- */
+/* Opt in: from here on the body paths (hgx_insert_event_bodies, _ext, hgx_insert_wire_bodies) keep every
+ * accepted event's R and transaction bytes in device memory, keyed by gid, and the consumers below
+ * serve them from there. Allowed on a context with no events (a fresh one, or after hgx_clear).
+ * tx_hint / bytes_hint: a first reservation in transactions and bytes (0 is allowed); the store grows
+ * by doubling when a chunk would not fit, a new allocation plus a device-to-device copy. If that
+ * allocation fails the insert returns HGX_ERR_CAPACITY before that chunk is inserted (earlier chunks of
+ * the call stay inserted). HGX_ERR_INVALID "hgx_keep_bodies: <reason>": NULL ctx, resident events,
+ * negative hints, a chain-sharded or row-sharded context.
+ * State rules: an insert that brings events without bodies (hgx_insert_events and its 32 / packed /
+ * _device / _verified forms, hgx_insert_wire_events, hgx_insert_and_run*, hgx_bootstrap) leaves the
+ * store lost: every consumer returns HGX_ERR_INVALID "<fn>: bodies not known" and nothing more is
+ * kept until hgx_clear (or hgx_reset), which empties the store and makes it complete again.
+ * hgx_prune_to_frame compacts the store with the events: kept events keep R and transactions under
+ * their new gids, the dropped events' bytes are released. That compaction runs before anything is
+ * dropped: if its allocation fails, or the kept bodies reach 4 GiB, hgx_prune_to_frame returns
+ * HGX_ERR_CAPACITY and the context, its events and the store are as they were. A context that never called hgx_keep_bodies
+ * takes exactly the paths, allocations and launches it took before. hgx_save does not store bodies. */
+int32_t hgx_keep_bodies(hgx_ctx* ctx, int64_t tx_hint, int64_t bytes_hint, hgx_error* err);
+/* 0 off, 1 complete, 2 lost; the events, transactions and bytes held (each pointer may be NULL) */
+int32_t hgx_bodies_state(hgx_ctx* ctx, int64_t* n_events, int64_t* n_tx, int64_t* n_bytes);
+/* R and the transactions of the events `gids` (any order, repeats allowed), as the sig_r / ntx / tx_off /
+ * tx_bytes columns of hgx_event_bodies in list order: ntx -1 = nil; tx_off holds *n_tx + 1 offsets from
+ * 0 (an array of tx_cap + 1 entries), tx_bytes *n_bytes bytes. A NULL array is not written.
+ * HGX_ERR_KEY_NOT_FOUND "<gid>, Not Found" for a gid outside [0, hgx_num_events), nothing written.
+ * HGX_ERR_CAPACITY when tx_cap < *n_tx or bytes_cap < *n_bytes (a NULL array has capacity 0): *n_tx
+ * and *n_bytes are set and no array is touched, so NULL arrays with capacities 0 make a sizing call.
+ * One call moves less than 4 GiB (HGX_ERR_CAPACITY beyond). HGX_ERR_INVALID "hgx_get_event_bodies:
+ * bodies not known" unless hgx_bodies_state is 1. */
+int32_t hgx_get_event_bodies(hgx_ctx* ctx, const int64_t* gids, int64_t count, uint8_t* sig_r, int32_t* ntx,
+                             int64_t* tx_off, int64_t tx_cap, uint8_t* tx_bytes, int64_t bytes_cap, int64_t* n_tx,
+                             int64_t* n_bytes, hgx_error* err);
+/* Block.Transactions of block b of `graph` (hashgraph.go:826-854): the transactions of the block's
+ * events in consensus order, from the body store; sizing and capacity rules of hgx_get_event_bodies.
+ * *n_tx equals hgx_block_info's n_tx (HGX_ERR_PANIC otherwise). HGX_ERR_TOO_LATE
+ * "hgx_block_transactions: block <b>: events no longer resident" after hgx_reset / hgx_prune_to_frame
+ * dropped them; HGX_ERR_KEY_NOT_FOUND "<b>, Not Found" for b outside the blocks. Callable from
+ * inside hgx_commit_fn. */
+int32_t hgx_block_transactions(hgx_ctx* ctx, int32_t graph, int64_t b, int64_t* tx_off, int64_t tx_cap,
+                               uint8_t* tx_bytes, int64_t bytes_cap, int64_t* n_tx, int64_t* n_bytes, hgx_error* err);
+/* Block.Hash (block.go:44-53) of block b of `graph`: on a keeping context in state 1 every hgx_find_order
+ * gathers its new blocks' transactions from the body store (the gid list is the device-resident order),
+ * encodes {"RoundReceived":N,"Transactions":T}\n and hashes it on the device, and stores 32 bytes with
+ * the block before the commit callbacks fire, so this is callable from inside hgx_commit_fn. The hashes
+ * survive hgx_reset / hgx_prune_to_frame as the blocks do. The hashes are computed before the call's
+ * blocks are recorded: if that fails (HGX_ERR_CAPACITY when one call's new blocks reach 4 GiB of
+ * transactions or text) hgx_find_order returns the error and has made no block. HGX_ERR_KEY_NOT_FOUND "<b>, Not Found" for b
+ * outside the blocks or a block made while the state was not 1; HGX_ERR_INVALID "hgx_get_block_hash:
+ * bodies not known" in states 0 and 2. */
+int32_t hgx_get_block_hash(hgx_ctx* ctx, int32_t graph, int64_t b, uint8_t* out32, hgx_error* err);
+/* The encoder alone (host pointers, no context): Block.Hash of `count` blocks on `device`. Block k has
+ * ntx[k] transactions, consecutive in tx_off (the sum of ntx, plus one, offsets into tx_bytes); its text
+ * prints null for tx_nil[k] && ntx[k] == 0, else the list ("" for an empty transaction). The texts are
+ * built in groups of at most 32 MiB (a single larger block raises the bound to its size); the whole
+ * batch's text stays below 4 GiB (HGX_ERR_CAPACITY beyond, decided on the host before any launch). out32: 32 bytes per block. The host twin is hgx_block_hash. */
+int32_t hgx_block_hash_batch(int32_t device, const int64_t* round_received, const int32_t* ntx,
+                             const int32_t* tx_nil, const int64_t* tx_off, const uint8_t* tx_bytes, int64_t count,
+                             uint8_t* out32, hgx_error* err);
+/* R and the transactions of hgx_diff_wire_bodies' rows: caller-allocated, sig_r `cap` rows of 32 bytes,
+ * tx_off tx_cap + 1 entries, tx_bytes bytes_cap bytes; a NULL array is skipped (capacity 0). */
+typedef struct {
+    uint8_t* sig_r;
+    int64_t* tx_off;
+    int64_t tx_cap;
+    uint8_t* tx_bytes;
+    int64_t bytes_cap;
+} hgx_wire_body_out;
+/* A complete SyncResponse: hgx_diff_wire (plan, launches, errors, the cap rule and the untouched outputs
+ * on error, all unchanged) plus R and the transactions of the first min(cap, *count) rows from the body
+ * store. *n_tx / *n_bytes are those rows' totals. If they do not fit body's capacities: HGX_ERR_CAPACITY
+ * with *count, *n_tx and *n_bytes set and no array written, so a NULL body (or capacities 0) with cap =
+ * the row count makes a sizing call. With ntx = tx_nil ? -1 : ntx the returned columns are directly the
+ * hgx_wire_bodies of hgx_insert_wire_bodies on the peer. HGX_ERR_INVALID "hgx_diff_wire_bodies: bodies
+ * not known" unless hgx_bodies_state is 1. */
+int32_t hgx_diff_wire_bodies(hgx_ctx* ctx, int32_t graph, const int32_t* known, int64_t sync_limit,
+                             hgx_wire_out* out, hgx_wire_body_out* body, int64_t cap, int64_t* count, int64_t* n_tx,
+                             int64_t* n_bytes, int32_t* over_limit, hgx_error* err);
 
 /* ---- per-event results (bulk) --------------------------------------------- */
 /* round (Round), witness (Witness), famous (RoundEvent.Famous: 0 Undefined,1 True,2 False) */
