@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
+#include <utility>
 
 namespace hgx {
 
@@ -87,6 +89,35 @@ struct Coord<uint16_t> {
 __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
+}
+
+// f(std::integral_constant<int, 0>) ... f(std::integral_constant<int, N - 1>): a loop whose index is a
+// compile-time constant in the body (register arrays indexed by it never go to scratch)
+template <int... I, class F>
+__device__ __forceinline__ void static_for_seq(std::integer_sequence<int, I...>, F&& f) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+    static_for_seq(std::make_integer_sequence<int, N>{}, f);
+}
+
+// the value lane (lane ^ D) of the wave holds, D a power of two, without LDS storage: DPP quad_perm for
+// D = 1, 2 and row_ror:8 for D = 8 (inside a row of 16 a rotation by 8 is the xor), ds_swizzle in bit
+// mode for D = 4, 16 (and 0x1F, xor D, inside each half of the wave), a bpermute across the halves.
+// Every lane of the wave must be active.
+template <int D>
+__device__ __forceinline__ uint32_t lane_xor_u32(uint32_t v) {
+    static_assert(D == 1 || D == 2 || D == 4 || D == 8 || D == 16 || D == 32, "lane distance");
+    if constexpr (D == 1) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);   // [1,0,3,2]
+    else if constexpr (D == 2) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);   // [2,3,0,1]
+    else if constexpr (D == 8) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, true);
+    else if constexpr (D == 32) return (uint32_t)__shfl_xor((int)v, 32);
+    else return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x1F | (D << 10));
+}
+template <int D>
+__device__ __forceinline__ uint64_t lane_xor_u64(uint64_t v) {
+    return ((uint64_t)lane_xor_u32<D>((uint32_t)(v >> 32)) << 32) | lane_xor_u32<D>((uint32_t)v);
 }
 
 __device__ __forceinline__ uint64_t wave_min_u64(uint64_t x) {

@@ -17,6 +17,7 @@
 #include <mutex>
 #include <tuple>
 
+#include "hgx.h"
 #include "hgx_device.h"
 #include "hgx_kernels.h"
 
@@ -1721,14 +1722,41 @@ struct SortFinish {
 };
 
 // One bucket per group of GS threads (a workgroup of 1 024 threads, or a wave, GS = 64, four buckets
-// per workgroup when every bucket holds <= 512 events: 256 threads per bucket at c3 left the LDS latency
-// of the compare-exchange stages exposed, 1.14 ms per pass): bitonic sort of its (key, value) pairs in LDS
-// (cap = the largest bucket rounded up to a power of two), then the runs of equal keys (same graph,
-// rr and timestamp) ordered by S in the same kernel: a run's members get the first 8 bytes of their S
-// (big-endian) in place of the key they share, and each member's place in its run is its rank by
-// (S prefix, full S on equal prefixes, index) -- the radix path's k_tie_prefix / k_tiefix_rank, with
-// the run in LDS (consensus_sorter.go:36-51). Writes the final values and finishes them (SortFinish).
-template <int GS, int TB>
+// per workgroup when every bucket holds <= 512 events): bitonic sort of the bucket with its elements in
+// registers, then the runs of equal keys (same graph, rr and timestamp) ordered by S in the same kernel.
+//
+// The network (round 13; the 78 stages of a 4 096-element bucket each went through LDS before, two key
+// reads and up to six more accesses per pair and a workgroup barrier per stage, LDS-bandwidth bound):
+// thread t of the group owns the EPT = CAP / GS consecutive elements i = EPT t + e, CAP the launch's cap
+// (the largest bucket rounded up to a power of two, at least GS); a bucket of len events runs the stages
+// (k, j) of its own P = 2^ceil(log2 len) <= CAP, elements [len, CAP) padded with the largest word.
+//   j < EPT            both partners in one thread: compare-exchange between registers
+//   EPT <= j < 64 EPT  partners in one wave at lane distance j / EPT: lane_xor (DPP, swizzle, bpermute)
+//   j >= 64 EPT        partners in two waves (GS = 1 024 only; P = 4 096: ten stages of the 78): the own
+//                      elements written to LDS, a barrier, the partners' read back
+// The lower element keeps the minimum in ascending blocks ((i & k) == 0), as the LDS network did.
+// PACK (the varying key bits + log2 CAP <= 64; the bits above are the bucket's own (graph, rr), shifted
+// out): one word (key << log2 CAP) | index is sorted and the value fetched from vin at the end -- half
+// the registers and exchanges, and the order among equal keys is by index whatever the network. The
+// cross-wave words ping-pong between the two halves of the bucket's LDS, one barrier per stage. Without
+// PACK (key, value) pairs travel, a pair swaps only on a strict inequality, and the cross-wave stages
+// use sk / sv with a barrier on either side.
+//
+// After the network the sorted keys and values go to sk / sv once, and a run's members get the first 8
+// bytes of their S (big-endian) in place of the key they share; each member's place in its run is its
+// rank by (S prefix, full S on equal prefixes, index) -- the radix path's k_tie_prefix / k_tiefix_rank,
+// with the run in LDS (consensus_sorter.go:36-51). Equal key and equal S (never in a valid trace): the
+// place follows the order the network left them in. Writes the final values and finishes them
+// (SortFinish).
+template <bool PACK>
+__device__ __forceinline__ void seg_cx(uint64_t& a, uint32_t& va, uint64_t b, uint32_t vb, bool keep_min) {
+    // (PACK: two words are equal only where both are padding, so one compare decides)
+    const bool take = PACK ? (b < a) == keep_min : (keep_min ? b < a : b > a);
+    a = take ? b : a;
+    if constexpr (!PACK) va = take ? vb : va;
+}
+
+template <int GS, int TB, int EPT, bool PACK>
 __global__ void __launch_bounds__(TB) k_seg_sort(int nseg, int seg0, int seg1, int32_t m, const uint32_t* __restrict__ segoff,
                                                   const uint64_t* __restrict__ kin, const uint32_t* __restrict__ vin,
                                                   const int32_t* __restrict__ p_gid, const uint8_t* __restrict__ g_S,
@@ -1737,6 +1765,8 @@ __global__ void __launch_bounds__(TB) k_seg_sort(int nseg, int seg0, int seg1, i
     __shared__ int64_t red_ntx[TB / 64];
     __shared__ int32_t red_ld[TB / 64];
     constexpr int NG = TB / GS;   // groups (buckets) per workgroup
+    constexpr int CAP = GS * EPT;   // (cap <= CAP: a wave's cap may be under 64)
+    constexpr int LOGCAP = __builtin_ctz(CAP);
     const int grp = (int)threadIdx.x / GS, t = (int)threadIdx.x % GS;
     uint64_t* sk = smem + (size_t)grp * cap;                               // [cap] keys, then S prefixes
     uint32_t* sv = (uint32_t*)(smem + (size_t)NG * cap) + (size_t)grp * cap;   // [cap] values
@@ -1788,28 +1818,105 @@ __global__ void __launch_bounds__(TB) k_seg_sort(int nseg, int seg0, int seg1, i
     }
     int P = 2;
     while (P < len) P <<= 1;
-    for (int i = t; i < P; i += GS) {
-        sk[i] = i < len ? kin[o + i] : ~0ull;
-        sv[i] = i < len ? vin[o + i] : 0u;
-    }
-    sync();
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int q = t; q < (P >> 1); q += GS) {
-                const int lo = 2 * j * (q / j) + (q & (j - 1)), hi = lo + j;
-                const bool asc = (lo & k) == 0;
-                const uint64_t a = sk[lo], b = sk[hi];
-                if ((a > b) == asc) {
-                    sk[lo] = b;
-                    sk[hi] = a;
-                    const uint32_t x = sv[lo];
-                    sv[lo] = sv[hi];
-                    sv[hi] = x;
-                }
+    const int ib = EPT * t;   // the thread's first element
+    uint64_t w[EPT];
+    uint32_t v[EPT];
+    static_for<EPT>([&](auto E) {
+        constexpr int e = decltype(E)::value;
+        const int i = ib + e;
+        w[e] = ~0ull;
+        v[e] = 0u;
+        if (i < len) {
+            const uint64_t key = kin[o + i];
+            if constexpr (PACK) {
+                w[e] = (key << LOGCAP) | (uint64_t)i;   // (below the padding: i < len <= CAP - 1 where there is any)
+            } else {
+                w[e] = key;
+                v[e] = vin[o + i];
             }
-            sync();
         }
-    }
+    });
+    [[maybe_unused]] int flip = 0;   // (PACK: the half of the bucket's LDS the next cross-wave stage uses)
+    static_for<LOGCAP>([&](auto LK) {
+        constexpr int k = 2 << decltype(LK)::value;
+        if (k <= P) {   // (group-uniform)
+            static_for<decltype(LK)::value + 1>([&](auto JJ) {
+                constexpr int j = (k >> 1) >> decltype(JJ)::value;
+                if constexpr (j < EPT) {
+                    static_for<EPT>([&](auto E) {
+                        constexpr int e = decltype(E)::value;
+                        if constexpr ((e & j) == 0) {
+                            bool asc;
+                            if constexpr (k < EPT) asc = (e & k) == 0; else asc = (ib & k) == 0;
+                            const bool sw = PACK ? (w[e] > w[e + j]) == asc : (asc ? w[e] > w[e + j] : w[e] < w[e + j]);
+                            const uint64_t a = w[e], b = w[e + j];
+                            w[e] = sw ? b : a;
+                            w[e + j] = sw ? a : b;
+                            if constexpr (!PACK) {
+                                const uint32_t x = v[e], y = v[e + j];
+                                v[e] = sw ? y : x;
+                                v[e + j] = sw ? x : y;
+                            }
+                        }
+                    });
+                } else if constexpr (j < 64 * EPT) {
+                    // (k > j >= EPT: neither bit lies in e)
+                    const bool keep_min = ((ib & j) == 0) == ((ib & k) == 0);
+                    static_for<EPT>([&](auto E) {
+                        constexpr int e = decltype(E)::value;
+                        const uint64_t b = lane_xor_u64<j / EPT>(w[e]);
+                        uint32_t vb = 0u;
+                        if constexpr (!PACK) vb = lane_xor_u32<j / EPT>(v[e]);
+                        seg_cx<PACK>(w[e], v[e], b, vb, keep_min);
+                    });
+                } else {
+                    const bool keep_min = ((ib & j) == 0) == ((ib & k) == 0);
+                    const bool in = ib < P;   // (the partner of an element under P lies under P)
+                    if constexpr (PACK) {
+                        uint64_t* xb = smem + (flip ? CAP : 0);   // (GS = 1 024: one bucket, cap == CAP)
+                        flip ^= 1;
+                        if (in) static_for<EPT>([&](auto E) { xb[ib + decltype(E)::value] = w[decltype(E)::value]; });
+                        __syncthreads();
+                        if (in)
+                            static_for<EPT>([&](auto E) {
+                                constexpr int e = decltype(E)::value;
+                                seg_cx<PACK>(w[e], v[e], xb[(ib ^ j) + e], 0u, keep_min);
+                            });
+                    } else {
+                        if (in)
+                            static_for<EPT>([&](auto E) {
+                                constexpr int e = decltype(E)::value;
+                                sk[ib + e] = w[e];
+                                sv[ib + e] = v[e];
+                            });
+                        __syncthreads();
+                        if (in)
+                            static_for<EPT>([&](auto E) {
+                                constexpr int e = decltype(E)::value;
+                                seg_cx<PACK>(w[e], v[e], sk[(ib ^ j) + e], sv[(ib ^ j) + e], keep_min);
+                            });
+                        __syncthreads();
+                    }
+                }
+            });
+        }
+    });
+    // the sorted bucket to sk / sv for the tie phase (PACK: the last cross-wave reads come first)
+    if constexpr (PACK && GS > 64) __syncthreads();
+    static_for<EPT>([&](auto E) {
+        constexpr int e = decltype(E)::value;
+        const int i = ib + e;
+        if (i < len) {
+            if constexpr (PACK) {
+                sk[i] = w[e] >> LOGCAP;   // (equal exactly when the keys are: the bits shifted out are the bucket's)
+                sv[i] = vin[o + (int)(w[e] & (uint64_t)(CAP - 1))];
+            } else {
+                sk[i] = w[e];
+                sv[i] = v[e];
+            }
+        }
+    });
+    sync();
     // run starts: inclusive max-scan of (head ? i : 0) over [0, len), ping-pong between rs[0] and rs[1]
     bool tie_any = false;
     for (int i = t; i < len; i += GS) {
@@ -2597,6 +2704,58 @@ void launch_seg_count(hipStream_t s, const DevArrays& a, int32_t m, int R, int n
                        max_out);
 }
 
+// the bucket sort of buckets [s0, s1): the instantiation of the launch's cap (a wave per bucket and four
+// per workgroup up to 512, a workgroup of 1 024 threads above; EPT = CAP / GS elements per thread) and of
+// PACK; launch = false only raises the 1 024-thread kernel's LDS limit (before anything is launched)
+namespace {
+struct SegSortArgs {
+    int nseg, s0, s1;
+    int32_t m;
+    const uint32_t* segoff;
+    const uint64_t* kin;
+    const uint32_t* vin;
+    const int32_t* p_gid;
+    const uint8_t* g_S;
+    uint32_t* vout;
+    int cap;
+    SortFinish F;
+};
+
+template <int GS, int TB, int EPT, bool PACK>
+hipError_t seg_sort_go(hipStream_t s, const SegSortArgs& g, bool launch) {
+    constexpr int NG = TB / GS;
+    const size_t lds = (size_t)NG * g.cap * 16;
+    if (!launch) return GS > 64 ? ensure_lds_limit((const void*)k_seg_sort<GS, TB, EPT, PACK>, lds) : hipSuccess;
+    hipLaunchKernelGGL((k_seg_sort<GS, TB, EPT, PACK>), dim3((g.s1 - g.s0 + NG - 1) / NG), dim3(TB), lds, s, g.nseg, g.s0,
+                       g.s1, g.m, g.segoff, g.kin, g.vin, g.p_gid, g.g_S, g.vout, g.cap, g.F);
+    return hipSuccess;
+}
+
+template <int GS, int TB, bool PACK>
+hipError_t seg_sort_ept(hipStream_t s, const SegSortArgs& g, bool launch) {
+    switch (std::max(1, g.cap / GS)) {
+        case 1: return seg_sort_go<GS, TB, 1, PACK>(s, g, launch);
+        case 2: return seg_sort_go<GS, TB, 2, PACK>(s, g, launch);
+        case 4: return seg_sort_go<GS, TB, 4, PACK>(s, g, launch);
+        case 8: return seg_sort_go<GS, TB, 8, PACK>(s, g, launch);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// (key_bits: the key bits that vary inside a bucket; the index takes log2 CAP bits, CAP >= 64)
+bool seg_sort_packs(int cap, int key_bits) {
+    int lc = 6;
+    while ((1 << lc) < cap) lc++;
+    return key_bits + lc <= 64;
+}
+
+hipError_t seg_sort_run(hipStream_t s, const SegSortArgs& g, bool pack, bool launch) {
+    if (g.cap <= 512)
+        return pack ? seg_sort_ept<64, 256, true>(s, g, launch) : seg_sort_ept<64, 256, false>(s, g, launch);
+    return pack ? seg_sort_ept<1024, 1024, true>(s, g, launch) : seg_sort_ept<1024, 1024, false>(s, g, launch);
+}
+}  // namespace
+
 hipError_t launch_sort_seg(hipStream_t s, const DevArrays& a, int32_t m, int64_t cmin, int cts_bits, int R, int n,
                            int nseg, uint32_t* segoff, uint32_t* segcur, int max_seg, uint32_t** final_vals,
                            uint64_t** final_keys, const std::vector<int>* cuts,
@@ -2605,33 +2764,28 @@ hipError_t launch_sort_seg(hipStream_t s, const DevArrays& a, int32_t m, int64_t
     uint32_t *va = a.val_a, *vb = a.val_b;
     int cap = 2;
     while (cap < max_seg) cap <<= 1;
-    if (cap > 512) {   // (before anything is launched: the caller takes the radix passes on a refusal)
-        const hipError_t e = ensure_lds_limit((const void*)k_seg_sort<1024, 1024>, (size_t)cap * 16);
+    if (cap > kSegSortCap) return hipErrorInvalidValue;
+    // (the runs of equal keys are ordered by S inside k_seg_sort: the final values land in va)
+    SegSortArgs g{nseg, 0, nseg, m, segoff, kb, vb, a.p_gid, a.g_S, va, cap,
+                  SortFinish{a.p_rr, a.p_cts, a.g_ntx, a.g_loaded, a.g_txnil, a.order_gid, a.g_rr, a.g_cts,
+                             a.blk_cnt, a.blk_ntx, a.blk_loaded, a.blk_nil}};
+    // (inside a bucket only the timestamp bits of the key vary)
+    const bool pack = seg_sort_packs(cap, cts_bits);
+    {   // (before anything is launched: the caller takes the radix passes on a refusal)
+        const hipError_t e = seg_sort_run(s, g, pack, false);
         if (e != hipSuccess) return e;
     }
     scan_u32(s, a, segoff, nseg);   // bucket counts -> bucket starts
     (void)hipMemsetAsync(segcur, 0, (size_t)nseg * 4, s);
     hipLaunchKernelGGL(k_seg_keys_scatter, dim3(nblk(m, 256)), dim3(256), 0, s, m, a.recv_list, a.p_cts, a.p_chain,
                        a.p_rr, cmin, cts_bits, R, n, segoff, segcur, kb, vb);
-    // (the runs of equal keys are ordered by S inside k_seg_sort: the final values land in va)
-    const SortFinish F{a.p_rr, a.p_cts, a.g_ntx, a.g_loaded, a.g_txnil, a.order_gid, a.g_rr, a.g_cts,
-                       a.blk_cnt, a.blk_ntx, a.blk_loaded, a.blk_nil};
     // the buckets in parts [cuts[k], cuts[k + 1]) (one part without cuts), after_part(k) behind each part's
     // launch (the caller's D2H of that part's order, overlapping the next part's sort)
     const int np = cuts ? (int)cuts->size() - 1 : 1;
     for (int k = 0; k < np; k++) {
-        const int s0 = cuts ? (*cuts)[k] : 0, s1 = cuts ? (*cuts)[k + 1] : nseg;
-        if (s1 > s0) {
-            if (cap <= 512) {   // a wave per bucket, four per workgroup
-                const size_t lds = (size_t)4 * cap * 16;
-                hipLaunchKernelGGL((k_seg_sort<64, 256>), dim3((s1 - s0 + 3) / 4), dim3(256), lds, s, nseg, s0, s1, m,
-                                   segoff, kb, vb, a.p_gid, a.g_S, va, cap, F);
-            } else {
-                const size_t lds = (size_t)cap * 16;
-                hipLaunchKernelGGL((k_seg_sort<1024, 1024>), dim3(s1 - s0), dim3(1024), lds, s, nseg, s0, s1, m, segoff,
-                                   kb, vb, a.p_gid, a.g_S, va, cap, F);
-            }
-        }
+        g.s0 = cuts ? (*cuts)[k] : 0;
+        g.s1 = cuts ? (*cuts)[k + 1] : nseg;
+        if (g.s1 > g.s0) (void)seg_sort_run(s, g, pack, true);
         if (after_part) {
             const hipError_t e = after_part(k);
             if (e != hipSuccess) return e;
@@ -2641,6 +2795,88 @@ hipError_t launch_sort_seg(hipStream_t s, const DevArrays& a, int32_t m, int64_t
     *final_keys = kb;
     return hipGetLastError();
 }
+
+// the bucket sort alone on caller-given buckets (hgx_seg_sort_check, include/hgx.h)
+hipError_t seg_sort_check_run(hipStream_t s, int nseg, int32_t m, int max_seg, int key_bits, bool force_kv,
+                              const uint32_t* segoff, const uint64_t* kin, const uint32_t* vin, const int32_t* p_gid,
+                              const uint8_t* g_S, uint32_t* vout, const SortFinish& F, bool* packed) {
+    int cap = 2;
+    while (cap < max_seg) cap <<= 1;
+    if (cap > kSegSortCap) return hipErrorInvalidValue;
+    const SegSortArgs g{nseg, 0, nseg, m, segoff, kin, vin, p_gid, g_S, vout, cap, F};
+    *packed = !force_kv && seg_sort_packs(cap, key_bits);
+    hipError_t e = seg_sort_run(s, g, *packed, false);
+    if (e == hipSuccess) e = seg_sort_run(s, g, *packed, true);
+    return e == hipSuccess ? hipGetLastError() : e;
+}
+
+}  // namespace hgx
+
+// Test entry (include/hgx.h): caller-given buckets through launch_sort_seg's kernels, with an identity
+// p_gid and scratch SortFinish targets.
+extern "C" int32_t hgx_seg_sort_check(int32_t device, int32_t nseg, const uint32_t* segoff, int32_t m,
+                                      const uint64_t* keys, const uint32_t* vals, const uint8_t* S32,
+                                      int32_t force_kv, uint32_t* out_vals, int32_t* packed_out) {
+    if (nseg < 1 || m < 1 || !segoff || !keys || !vals || !S32 || !out_vals) return HGX_ERR_INVALID;
+    // buckets: starts non-decreasing from 0, the last one ends at m; no bucket over the cap; values are S rows
+    int64_t max_seg = 0;
+    uint64_t all = 0;
+    if (segoff[0] != 0) return HGX_ERR_INVALID;
+    for (int sg = 0; sg < nseg; sg++) {
+        const int64_t b = segoff[sg], e = sg + 1 < nseg ? (int64_t)segoff[sg + 1] : (int64_t)m;
+        if (e < b || e > m) return HGX_ERR_INVALID;
+        max_seg = std::max(max_seg, e - b);
+    }
+    for (int32_t i = 0; i < m; i++) {
+        if (vals[i] >= (uint32_t)m) return HGX_ERR_INVALID;
+        all |= keys[i];
+    }
+    if (max_seg > hgx::seg_sort_cap()) return HGX_ERR_INVALID;
+    int key_bits = 0;
+    while (key_bits < 64 && (all >> key_bits) != 0) key_bits++;
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    if (hipSetDevice(device) != hipSuccess) return HGX_ERR_DEVICE;
+    // one allocation: keys, the 8-byte scratch columns, S, then the 4-byte and 1-byte columns
+    const size_t M = (size_t)m, NS = (size_t)nseg;
+    const size_t o_keys = 0, o_cts = o_keys + 8 * M, o_gcts = o_cts + 8 * M, o_bntx = o_gcts + 8 * M,
+                 o_S = o_bntx + 8 * NS, o_vin = o_S + 32 * M, o_vout = o_vin + 4 * M, o_gid = o_vout + 4 * M,
+                 o_prr = o_gid + 4 * M, o_ntx = o_prr + 4 * M, o_ogid = o_ntx + 4 * M, o_grr = o_ogid + 4 * M,
+                 o_off = o_grr + 4 * M, o_bcnt = o_off + 4 * NS, o_bld = o_bcnt + 4 * NS, o_ld = o_bld + 4 * NS,
+                 o_nil = o_ld + M, o_bnil = o_nil + M, total = o_bnil + NS;
+    uint8_t* d = nullptr;
+    hipStream_t s = nullptr;
+    bool packed = false;
+    std::vector<int32_t> ident(M);
+    for (int32_t i = 0; i < m; i++) ident[(size_t)i] = i;
+    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc((void**)&d, total);
+    if (e == hipSuccess) e = hipMemsetAsync(d, 0, total, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_keys, keys, 8 * M, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_S, S32, 32 * M, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_vin, vals, 4 * M, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_gid, ident.data(), 4 * M, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_off, segoff, 4 * NS, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+        const hgx::SortFinish F{(const int32_t*)(d + o_prr), (const int64_t*)(d + o_cts), (const int32_t*)(d + o_ntx),
+                                d + o_ld, d + o_nil, (int32_t*)(d + o_ogid), (int32_t*)(d + o_grr),
+                                (int64_t*)(d + o_gcts), (int32_t*)(d + o_bcnt), (int64_t*)(d + o_bntx),
+                                (int32_t*)(d + o_bld), d + o_bnil};
+        e = hgx::seg_sort_check_run(s, nseg, m, (int)max_seg, key_bits, force_kv != 0, (const uint32_t*)(d + o_off),
+                                    (const uint64_t*)(d + o_keys), (const uint32_t*)(d + o_vin),
+                                    (const int32_t*)(d + o_gid), d + o_S, (uint32_t*)(d + o_vout), F, &packed);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_vals, d + o_vout, 4 * M, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (d) (void)hipFree(d);
+    if (s) (void)hipStreamDestroy(s);
+    (void)hipSetDevice(prev);
+    if (e != hipSuccess) return HGX_ERR_DEVICE;
+    if (packed_out) *packed_out = packed ? 1 : 0;
+    return HGX_OK;
+}
+
+namespace hgx {
 
 void launch_root_floor(hipStream_t s, const DevArrays& a, const int32_t* root_round, int32_t* gfl, int32_t* gB,
                        int gmax, int C, int n, int max_len) {

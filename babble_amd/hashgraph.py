@@ -1233,6 +1233,25 @@ def sha256_bench(count: int, min_len: int, max_len: int, seed: int = 5, warmup: 
     return {"ms_per_launch": ms.value, "bytes": tot.value, "blocks": nb.value, "sample": sample}
 
 
+def seg_sort_check(segoff, keys, vals, S, force_kv: bool = False, device: int = 0):
+    """FindOrder's bucket sort on caller-given buckets (hgx_seg_sort_check): bucket b is elements
+    [segoff[b], segoff[b + 1]) of (keys, vals), the last one ends at len(keys); vals are rows of S [m, 32].
+    Returns (the values of every bucket ordered by (key, S row), whether the one-word path ran)."""
+    so = np.ascontiguousarray(segoff, np.uint32)
+    k = np.ascontiguousarray(keys, np.uint64)
+    v = np.ascontiguousarray(vals, np.uint32)
+    s = np.ascontiguousarray(S, np.uint8).reshape(-1, 32)
+    m = k.shape[0]
+    assert v.shape[0] == m and s.shape[0] == m
+    out = np.zeros(m, np.uint32)
+    packed = C.c_int32()
+    rc = _lib.lib().hgx_seg_sort_check(device, so.shape[0], ptr(so), m, ptr(k), ptr(v), ptr(s), int(bool(force_kv)),
+                                       ptr(out), C.byref(packed))
+    if rc:
+        raise HgxError(rc, "hgx_seg_sort_check failed")
+    return out, bool(packed.value)
+
+
 def _p256_cols(keys65, key_idx, digest, r, s):
     k = np.ascontiguousarray(keys65, np.uint8).reshape(-1, 65)
     cols = [np.ascontiguousarray(key_idx, np.int32)] + [np.ascontiguousarray(x, np.uint8).reshape(-1, 32)

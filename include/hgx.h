@@ -754,6 +754,17 @@ int32_t hgx_sha256_bench(int32_t device, int64_t count, int32_t min_len, int32_t
  * launch of `rounds` rounds after a warm-up launch; chains = 2 is one 1-to-1 hand-off each way. */
 int32_t hgx_exchange_floor_bench(int32_t device, int32_t chains, int32_t n, int32_t rounds, double* us_per_round);
 
+/* Test entry: FindOrder's bucket sort (k_seg_sort, the kernels launch_sort_seg runs) on caller-given
+ * buckets. Bucket b holds elements [segoff[b], segoff[b + 1]) of the m (key, value) pairs (segoff[0] = 0,
+ * the last bucket ends at m; no bucket over 8 192 elements); a value is a row of the m 32-byte rows S32,
+ * values < m. out_vals[m]: every bucket's values ordered by (key, S row as a big-endian number). The
+ * kernel instantiation follows the largest bucket as in FindOrder; the one-word path (key and index in
+ * 64 bits) is taken when the highest set bit of any key leaves room for the index, unless force_kv is
+ * nonzero; *packed_out (optional) = 1 when it was taken. */
+int32_t hgx_seg_sort_check(int32_t device, int32_t nseg, const uint32_t* segoff, int32_t m, const uint64_t* keys,
+                           const uint32_t* vals, const uint8_t* S32, int32_t force_kv, uint32_t* out_vals,
+                           int32_t* packed_out);
+
 /* ---- ingest front end: batched ECDSA P-256 verify ------ */
 /* Event.Verify (hashgraph/event.go:142-152) for a whole sync batch: crypto.ToECDSAPub of
  * Body.Creator (crypto/utils.go:22-28) and crypto.Verify (crypto/utils.go:41-43) = Go's
