@@ -13,12 +13,6 @@
 
 namespace hgx {
 
-#define HGX_TRY(x)                              \
-    do {                                        \
-        hipError_t _e = (x);                    \
-        if (_e != hipSuccess) return _e;        \
-    } while (0)
-
 template <typename T>
 hipError_t DBuf<T>::alloc(size_t count) {
     release();
@@ -231,8 +225,8 @@ hipError_t Engine::init(int device, int n_graphs, int n_part, int64_t cap_events
     fd_ld = (Ppos + 31) & ~(int64_t)31;   // firstDescendants columns: 64-byte aligned 32-position segments
     HGX_TRY(LA.alloc(PP * n));
     HGX_TRY(FDT.alloc((size_t)fd_ld * n + 128));   // slack: compact window staging reads past a column
-    HGX_TRY(recv_list.alloc(P)); HGX_TRY(counters.alloc(8 + 4 * kLaRing));
-    HGX_TRY(hipMemsetAsync(counters.p, 0, (8 + 4 * kLaRing) * 4, stream)); HGX_TRY(order_gid.alloc(P));
+    HGX_TRY(recv_list.alloc(P)); HGX_TRY(counters.alloc(kCtWords));
+    HGX_TRY(hipMemsetAsync(counters.p, 0, kCtWords * 4, stream)); HGX_TRY(order_gid.alloc(P));
     HGX_TRY(scan_part.alloc((size_t)256 * ((P + 2047) / 2048 + 1) / 2048 + 64));
     HGX_TRY(key_a.alloc(P)); HGX_TRY(key_b.alloc(P)); HGX_TRY(val_a.alloc(P)); HGX_TRY(val_b.alloc(P));
     HGX_TRY(hist.alloc((size_t)256 * ((P + 2047) / 2048 + 1)));
@@ -241,7 +235,7 @@ hipError_t Engine::init(int device, int n_graphs, int n_part, int64_t cap_events
     for (auto& e : la_ev) HGX_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     HGX_TRY(hipEventCreateWithFlags(&flag_ev[0], hipEventDisableTiming));
     HGX_TRY(hipEventCreateWithFlags(&flag_ev[1], hipEventDisableTiming));
-    HGX_TRY(hipHostMalloc((void**)&h_small, 64 * sizeof(int32_t), hipHostMallocDefault));
+    HGX_TRY(hipHostMalloc((void**)&h_small, kHsWords * sizeof(int32_t), hipHostMallocDefault));
     HGX_TRY(hipHostMalloc((void**)&h_flag, 16 * sizeof(int32_t), hipHostMallocMapped | hipHostMallocCoherent));
     HGX_TRY(hipHostGetDevicePointer((void**)&d_flag, h_flag, 0));
     // rounds: initial guess, grown on demand
@@ -790,8 +784,8 @@ hipError_t Engine::insert_impl(const InsertIn& in, int64_t count, InsertOut& out
             launch_insert_commit(stream, count, ins_fail.p, fail_sig, E0, n, in, st, commit_mode);
             launch_insert_unclaim(stream, count, ins_fail.p, fail_sig, E0, cap, C, in, st);
         }
-        HGX_TRY(copy_to_pinned(h_small, ins_fail.p, 8, 0xFF));
-        if (fail_sig) HGX_TRY(copy_to_pinned(h_small + 2, fail_sig, 8));
+        HGX_TRY(copy_to_pinned(h_small + kHsInsFail, ins_fail.p, 8, 0xFF));
+        if (fail_sig) HGX_TRY(copy_to_pinned(h_small + kHsInsFailSig, fail_sig, 8));
     }
     // the first-failure words and the whole state block into pinned memory (one launch), then
     // the host mirrors
@@ -800,8 +794,8 @@ hipError_t Engine::insert_impl(const InsertIn& in, int64_t count, InsertOut& out
     HGX_TRY(hipStreamSynchronize(stream));
     if (count > 0) {
         unsigned long long fail = 0, fsig = ~0ull;
-        std::memcpy(&fail, h_small, 8);
-        if (fail_sig) std::memcpy(&fsig, h_small + 2, 8);
+        std::memcpy(&fail, h_small + kHsInsFail, 8);
+        if (fail_sig) std::memcpy(&fsig, h_small + kHsInsFailSig, 8);
         // Verify comes first in InsertEvent: at the same event the signature's failure wins
         // (the kernels' accepted_prefix)
         if ((fsig >> 8) <= (fail >> 8) && fsig != ~0ull) fail = fsig;
@@ -977,7 +971,7 @@ hipError_t Engine::insert_pipe32(const HostCols& hc, int64_t count, InsertOut& o
         return hipSuccess;   // (an unknown creator, or very uneven chains: the serial path)
     }
     compact = plan_compact;
-    layout_slots(count, len, pipe_off);
+    layout_slots(C, Ppos, count, len.data(), pipe_off);
     std::memcpy(h_cpar, len.data(), Cz * 4);
     std::memset(h_cpar + C, 0, 2 * Cz * 4);   // c_base, c_old
     PIPE_TRY(hipMemcpyAsync(c_off.p, pipe_off.data(), (Cz + 1) * 4, hipMemcpyHostToDevice, stream));
@@ -1001,7 +995,7 @@ hipError_t Engine::insert_pipe32(const HostCols& hc, int64_t count, InsertOut& o
         LaSubset sub;
         sub.first = seg_cut[k]; sub.count = seg_cut[k + 1] - seg_cut[k];
         sub.c_lim = pipe_buf.p + o_lim + (size_t)k * Cz; sub.gate = gate;
-        PIPE_TRY(launch_la_wave(side, a, 1, n, nullptr, count, nts, 0, counters.p + 6, nullptr, n, false, sub));
+        PIPE_TRY(launch_la_wave(side, a, 1, n, nullptr, count, nts, 0, counters.p + kCtWaveErr, nullptr, n, false, sub));
     }
     PIPE_TRY(hipEventRecord(ev_side[0], stream_o));
     PIPE_TRY(hipStreamWaitEvent(stream, ev_side[0], 0));
@@ -1010,13 +1004,13 @@ hipError_t Engine::insert_pipe32(const HostCols& hc, int64_t count, InsertOut& o
         PIPE_TRY(hipStreamWaitEvent(stream, ev_side[1], 0));
     }
     // one read-back, as insert_impl: the first-failure word (re-armed) and the state block
-    PIPE_TRY(copy_to_pinned(h_small, ins_fail.p, 8, 0xFF));
+    PIPE_TRY(copy_to_pinned(h_small + kHsInsFail, ins_fail.p, 8, 0xFF));
     PIPE_TRY(copy_to_pinned(h_ins, ins_blk.p, ins_blk.n * sizeof(int32_t)));
     PIPE_TRY(stage_issue());
     PIPE_TRY(hipStreamSynchronize(stream));   // (behind every piece's event: the structure columns are read completely)
 #undef PIPE_TRY
     unsigned long long fail = 0;
-    std::memcpy(&fail, h_small, 8);
+    std::memcpy(&fail, h_small + kHsInsFail, 8);
     if (fail != ~0ull) {
         // a check failed in some piece: stop the copier, empty the context again (the claims of every
         // piece issued so far included) and let the serial path produce the error and the accepted
@@ -1384,66 +1378,6 @@ hipError_t Engine::reserve_rounds(int32_t rounds) {
     return hipStreamSynchronize(stream);
 }
 
-// nb round-step nodes captured as one hipGraph (their round arguments are rewritten per replay)
-hipError_t Engine::capture_steps(StepGraph& sgr, const RoundArgs& args, int kern, int nb) {
-    sgr.drop();
-    sgr.args = args;
-    sgr.kernel = kern;
-    sgr.compact = compact;
-    sgr.nb = nb;
-    HGX_TRY(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    hipError_t le = hipSuccess;   // a failed launch ends the capture, then is reported
-    for (int k = 0; k < nb && le == hipSuccess; k++) le = launch_round_step(stream, sgr.args, k, kern);
-    const hipError_t ce = hipStreamEndCapture(stream, &sgr.graph);
-    if (le != hipSuccess) {
-        if (ce == hipSuccess && sgr.graph) (void)hipGraphDestroy(sgr.graph);
-        sgr.graph = nullptr;
-        return le;
-    }
-    HGX_TRY(ce);
-    HGX_TRY(hipGraphInstantiate(&sgr.exec, sgr.graph, nullptr, nullptr, 0));
-    // the step nodes in launch order (a linear chain)
-    size_t nn = 0;
-    HGX_TRY(hipGraphGetNodes(sgr.graph, nullptr, &nn));
-    std::vector<hipGraphNode_t> nodes(nn);
-    HGX_TRY(hipGraphGetNodes(sgr.graph, nodes.data(), &nn));
-    sgr.nodes.clear();
-    sgr.params.clear();
-    hipGraphNode_t nd_cur = nullptr;
-    for (auto nd : nodes) {
-        size_t nd_deps = 0;
-        HGX_TRY(hipGraphNodeGetDependencies(nd, nullptr, &nd_deps));
-        if (nd_deps == 0) nd_cur = nd;
-    }
-    while (nd_cur) {
-        hipKernelNodeParams kp;
-        HGX_TRY(hipGraphKernelNodeGetParams(nd_cur, &kp));
-        sgr.nodes.push_back(nd_cur);
-        sgr.params.push_back(kp);
-        size_t nd_out = 0;
-        HGX_TRY(hipGraphNodeGetDependentNodes(nd_cur, nullptr, &nd_out));
-        if (nd_out == 0) break;
-        std::vector<hipGraphNode_t> outs(nd_out);
-        HGX_TRY(hipGraphNodeGetDependentNodes(nd_cur, outs.data(), &nd_out));
-        nd_cur = outs[0];
-    }
-    if ((int)sgr.nodes.size() != nb) return hipErrorUnknown;
-    return hipSuccess;
-}
-
-// The slots of a rebuilt layout and the time segments of its lastAncestors pass: one place for
-// divide_rounds and the pipelined ingest, which lays the chains out before divide_rounds runs
-void Engine::layout_slots(int64_t En, const std::vector<int32_t>& chain_len, std::vector<int32_t>& off) const {
-    int act = 0;
-    for (int c = 0; c < C; c++) act += chain_len[c] > 0 ? 1 : 0;
-    const int64_t share = (Ppos - En) / (2 * (int64_t)act + (C - act));
-    off.assign(C + 1, 0);
-    // slots of multiples of 32 positions (a share >= 128 > 31: Ppos >= capacity + 256 C): every
-    // chain starts 64-byte aligned in the firstDescendants columns (the round kernels' staging)
-    for (int c = 0; c < C; c++)
-        off[c + 1] = off[c] + ((chain_len[c] + (int32_t)((chain_len[c] > 0 ? 2 : 1) * share)) & ~31);
-}
-
 int Engine::rebuild_segments(int64_t En, int coord_compact) const {
     if (G != 1 || En < (int64_t)kLaSegMinRows * C) return 1;
     // as many segments as the CUs hold, of at least 2 x kLaHeadRows rows per chain: c2 (64 chains
@@ -1452,648 +1386,6 @@ int Engine::rebuild_segments(int64_t En, int coord_compact) const {
     // (the round-4 cap of kLaMaxSegs alone: c2 2.04 ms)
     const int cap_segs = (int)std::max<int64_t>(kLaMaxSegs, En / C / (2 * kLaHeadRows));
     return la_segs_override > 0 ? la_segs_override : la_wave_segments(n, coord_compact, num_cus, cap_segs);
-}
-
-// ---- DivideRounds ---------------------------------------------------------------
-// Chains are laid out with slack (positions [c_off[c], c_off[c] + slot)), so that a call
-// after more InsertEvents only appends rows: the events of earlier calls keep their
-// positions, lastAncestors rows and rounds, and the call works on the new events (DESIGN.md
-// §3.7). The layout is rebuilt (and everything recomputed) when a chain outgrows its slot,
-// the coordinate storage changes, or after reset_received / reserve_rounds / clear.
-hipError_t Engine::divide_rounds(int64_t En, const std::vector<int32_t>& chain_len,
-                                 const std::vector<int32_t>& chain_base, RoundsHost& out) {
-    stage_out.clear();   // every earlier call synchronized: the staging is free
-    pend.clear();
-    stage_used = 0;
-    int32_t max_index = -1;
-    int new_max_len = 0;
-    for (int c = 0; c < C; c++) {
-        if (chain_len[c] > 0) max_index = std::max(max_index, chain_base[c] + chain_len[c] - 1);
-        new_max_len = std::max(new_max_len, chain_len[c]);
-    }
-    // compact (uint16) coordinates when every Index fits below the sentinels
-    // (Coord<uint16_t>, hgx_device.h) and rows are whole dwords
-    const int new_compact = (!force_coord32 && (n % 2) == 0 && max_index <= 65533) ? 1 : 0;
-    bool rebuild = !laid_out || E_div == 0 || new_compact != compact || !incremental;
-    if (!rebuild)
-        for (int c = 0; c < C; c++)
-            if (chain_len[c] > h_off[c + 1] - h_off[c]) { rebuild = true; break; }
-    const int64_t E0 = rebuild ? 0 : E_div;
-    E = En;
-    compact = new_compact;
-    max_len = new_max_len;
-    const size_t csz = compact ? 2 : 4;
-    if (rebuild) {
-        // slack in shares: two for a chain with events, one for a chain without (a silent peer, or
-        // one that has not created an event yet). With even shares c5's 341 silent peers held a
-        // third of the slack and the live chains outgrew theirs two thirds through the run (an
-        // 18.8 ms rebuild call)
-        layout_slots(En, chain_len, h_off);
-        HGX_TRY(hipMemcpyAsync(c_off.p, h_off.data(), (C + 1) * 4, hipMemcpyHostToDevice, stream));
-        h_len_div.assign(C, 0);
-        last_rebuild = true;
-    } else {
-        last_rebuild = false;
-    }
-    // c_len | c_base | c_old in one copy from pinned staging (the previous call's copy has
-    // completed: every call synchronizes before returning)
-    std::memcpy(h_cpar, chain_len.data(), (size_t)C * 4);
-    std::memcpy(h_cpar + C, chain_base.data(), (size_t)C * 4);
-    std::memcpy(h_cpar + 2 * C, h_len_div.data(), (size_t)C * 4);
-    HGX_TRY(copy_from_pinned(cpar_blk.p, h_cpar, (size_t)3 * C * 4));
-    HGX_TRY(stage_issue());
-    // first round whose step can change: the lowest round of the last old event of a chain
-    // that got new events (every boundary below it is among old events)
-    int32_t r_lo = 0;
-    if (!rebuild) {
-        r_lo = 0x7FFFFFFF;
-        const int32_t Rp = out.R;
-        for (int c = 0; c < C && r_lo > 0; c++) {
-            if (chain_len[c] <= h_len_div[c]) continue;
-            const int32_t last = h_len_div[c] - 1;
-            if (last < 0 || Rp == 0) { r_lo = 0; break; }
-            int32_t lo = 0, hi = Rp;   // largest r in [0, Rp] with bm[r][c] <= last
-            while (lo < hi) {
-                const int32_t mid = (lo + hi + 1) / 2;
-                if (out.bm[(size_t)mid * C + c] <= last) lo = mid; else hi = mid - 1;
-            }
-            r_lo = std::min(r_lo, lo);
-        }
-        if (r_lo == 0x7FFFFFFF) r_lo = 0;
-    }
-    int max_new = 0;
-    for (int c = 0; c < C; c++) max_new = std::max(max_new, chain_len[c] - h_len_div[c]);
-    DevArrays a = arrays();
-    HGX_TRY(hipEventRecord(ph0, stream));
-    const int seg = kLaSeg;
-    // lastAncestors: fixed point from all -1 (new rows), dirty-tracked sweeps (k_la_sweep)
-    const size_t nunits = (size_t)((max_len + seg - 1) / seg) * C;
-    int64_t u0 = 0;
-    // above 896 chains a workgroup cannot give every chain a lane: one graph gets lanes for
-    // the chains that have events only (silent peers have none)
-    int la_na = n;
-    const int32_t* la_map = nullptr;
-    if (n > 896 && G == 1) {
-        h_lmap.clear();
-        for (int c = 0; c < C; c++)
-            if (chain_len[c] > 0) h_lmap.push_back(c);
-        la_na = (int)h_lmap.size();
-        if (la_na <= 896) {
-            if (la_lmap.n < (size_t)std::max(1, la_na)) HGX_TRY(la_lmap.alloc((size_t)n));
-            HGX_TRY(hipMemcpyAsync(la_lmap.p, h_lmap.data(), (size_t)la_na * 4, hipMemcpyHostToDevice, stream));
-            la_map = la_lmap.p;
-        }
-    }
-    la_wave_used = la_kernel == 0 && la_wave_ok(n, max_len, la_na) && (n <= 896 || la_map);
-    // a rebuild of one large graph runs the wavefront on time segments in parallel (their
-    // rows are lower bounds), then a verify sweep and the dirty sweeps complete them
-    // the pipelined ingest laid these events out and ran the main pass of its segments already
-    const bool piped = pipe_ready && rebuild && la_wave_used && !la_map && pipe_nts > 1 && En == pipe_En &&
-                       compact == pipe_compact && h_off == pipe_off;
-    pipe_ready = false;
-    la_wave_segs = piped ? pipe_nts : (la_wave_used && rebuild) ? rebuild_segments(En, compact) : 1;
-    kbeg(K_LAYOUT);
-    if (!piped) launch_layout(stream, E0, En, a, C, n, seg);
-    kend(K_LAYOUT, (double)(En - E0) * 64);
-    if (rebuild) {   // (the wavefront writes every row it builds before anything reads it)
-        if (!la_wave_used) HGX_TRY(hipMemsetAsync(LA.p, compact ? 0x00 : 0xFF, (size_t)h_off[C] * n * csz, stream));
-    } else {
-        launch_init_new(stream, a, E0, En - E0, n, fd_ld);
-        int32_t smin = 0x7FFFFFFF;
-        for (int c = 0; c < C; c++)
-            if (chain_len[c] > h_len_div[c]) smin = std::min(smin, h_len_div[c] / seg);
-        u0 = (int64_t)smin * C;
-    }
-    if (la_chg.n < nunits) {   // change stamps: new units start at 0, a stamp no sweep uses
-        const size_t old = la_chg.n;
-        HGX_TRY(la_chg.grow_copy(std::max(nunits, 2 * la_chg.n), old, stream));
-        HGX_TRY(hipMemsetAsync(la_chg.p + old, 0, (la_chg.n - old) * 4, stream));
-    }
-    if (la_usum.n < nunits) HGX_TRY(la_usum.grow_copy(std::max(nunits, 2 * la_usum.n), la_usum.n, stream));
-    const int32_t* cold = rebuild ? nullptr : c_old.p;
-    la_sweeps = 0;
-    la_rows = 0;
-    auto run_sweeps = [&](int first_mode) -> hipError_t {
-        // sweep k's counters in ring slot k % kLaRing; up to kLaAhead sweeps are queued
-        // before the host reads the oldest one's "units changed" (a sweep after the one that
-        // changed nothing finds no dirty unit and does nothing)
-        // dirty flags are sweep stamps (monotone over calls: stale ones never match), so a
-        // sweep is one kernel, one 8-byte read-back and one event
-        int launched_s = 0;
-        HGX_TRY(hipMemsetAsync(counters.p + 8, 0, 16, stream));
-        auto launch_sweep = [&]() -> hipError_t {
-            const int slot = launched_s % kLaRing;
-            int32_t* cnt = counters.p + 8 + 4 * slot;
-            int32_t* cnt_next = counters.p + 8 + 4 * ((launched_s + 1) % kLaRing);
-            kbeg(K_LA_SWEEP);
-            launch_la_sweep(stream, a, C, n, max_len, seg, launched_s == 0 ? first_mode : 0, la_chg.p, ++la_stamp,
-                            la_usum.p, cnt, cnt_next, cold, u0);
-            kend(K_LA_SWEEP, 0);
-            HGX_TRY(hipMemcpyAsync(h_small + 16 + 4 * slot, cnt, 8, hipMemcpyDeviceToHost, stream));
-            HGX_TRY(hipEventRecord(la_ev[slot], stream));
-            launched_s++;
-            return hipSuccess;
-        };
-        for (;;) {
-            // a verify sweep usually finds nothing to redo: wait for it before queueing more
-            const int ahead = (first_mode == 2 && la_sweeps == 0) ? 1 : kLaAhead;
-            while (launched_s < la_sweeps + ahead) HGX_TRY(launch_sweep());
-            const int slot = la_sweeps % kLaRing;
-            HGX_TRY(hipEventSynchronize(la_ev[slot]));
-            const int32_t rows = h_small[16 + 4 * slot], changed = h_small[16 + 4 * slot + 1];
-            // algorithmic bytes of the rows this sweep recomputed (read the two
-            // parent rows, write the row, 12n + 16; the self-parent row is the register carry)
-            la_rows += rows;
-            kadd_bytes(K_LA_SWEEP, (double)rows * (3.0 * csz * n + 16));
-            la_sweeps++;
-            if (changed == 0) break;
-            if (la_sweeps > 100000) return hipErrorUnknown;
-        }
-        return hipSuccess;
-    };
-    if (la_wave_used) {
-        // one dataflow pass (k_la_wave); its error flag is read with the phase clock below
-        // the error flag is 0 here: zeroed at creation, re-armed by every read
-        kbeg(K_LA_SWEEP);
-        // a small graph (c1) entirely in one workgroup's LDS
-        int64_t gpos = 0;   // the most events of a graph
-        for (int g = 0; g < G && la_wave_segs == 1 && !la_map; g++) {
-            int64_t e = 0;
-            for (int c = 0; c < n; c++) e += chain_len[(size_t)g * n + c];
-            gpos = std::max(gpos, e);
-        }
-        const size_t small_lds = (la_wave_segs == 1 && !la_map && la_small_override != 0) ? la_small_bytes(n, compact, gpos) : 0;
-        la_small_used = small_lds > 0;
-        if (la_small_used) HGX_TRY(launch_la_small(stream, a, G, n, cold, small_lds, counters.p + 6));
-        else if (!piped)
-            HGX_TRY(launch_la_wave(stream, a, G, n, cold, En, la_wave_segs, 0, counters.p + 6, la_map, la_na,
-                                   !rebuild && (En - E0) <= 8 * (int64_t)C));
-        if (la_wave_segs > 1)
-            HGX_TRY(launch_la_wave(stream, a, G, n, nullptr, En, la_wave_segs, kLaHeadRows, counters.p + 6, la_map, la_na));
-        const double rows = (double)(En - E0);
-        kend(K_LA_SWEEP, rows * (3.0 * csz * n + 16));
-        if (rebuild) {
-            HGX_TRY(hipMemcpyAsync(h_small + 48, counters.p + 6, 4, hipMemcpyDeviceToHost, stream));
-            HGX_TRY(hipMemsetAsync(counters.p + 6, 0, 4, stream));
-        }
-        if (la_wave_segs > 1) {
-            // the verify sweep (+ dirty sweeps, counted there) only when the segments' exactness check
-            // fails (k_la_seg_check): c3 1.6 ms per pass otherwise
-            const size_t nt = (size_t)(la_wave_segs + 1) * n;
-            if (la_chk.n < nt + 1) HGX_TRY(la_chk.alloc(nt + 1));
-            HGX_TRY(hipMemsetAsync(la_chk.p, 0, 4, stream));
-            HGX_TRY(launch_la_seg_check(stream, a, n, En, la_wave_segs, kLaHeadRows, la_chk.p + 1, la_chk.p));
-            HGX_TRY(hipMemcpyAsync(h_small + 50, la_chk.p, 4, hipMemcpyDeviceToHost, stream));
-            HGX_TRY(hipStreamSynchronize(stream));
-            la_verified = h_small[50] != 0 || la_verify_always;
-            if (la_verified) HGX_TRY(run_sweeps(2));
-        }
-        la_sweeps++;
-        la_rows += (int64_t)rows;
-    } else {
-        HGX_TRY(run_sweeps(1));
-    }
-    // the compact payload of hgx_insert_and_run32 / _packed: its first columns started with this call
-    // (or right behind the pipelined ingest's last piece) and have crossed PCIe under lastAncestors,
-    // so they are committed here, ahead of the rounds and their coin pass, and nothing of the payload
-    // is left between the recurrence and DecideFame. (Not earlier: issuing a copy from pageable memory
-    // returns only once its source is consumed, and the wait for that would hold up the launches above.)
-    // After a pipelined ingest its second side stream is idle (its segments were joined before the
-    // ingest returned, and so was the layout): the commit runs there beside k_fd_build, which neither
-    // reads nor writes what it touches, and the context stream takes it up again before the rounds.
-    bool side_commit = false;
-    if (pay_commit_pending && pay_S_pending && !grp) {
-        side_commit = piped && stream_p != nullptr && time_mask == 0;
-        HGX_TRY(payload_commit(true, side_commit ? stream_p : stream));
-        if (side_commit) HGX_TRY(hipEventRecord(ev_side[1], stream_p));
-    }
-    kbeg(K_FD_BUILD);
-    if (grp) {   // a chain-sharded group (one graph): the firstDescendants of this shard's chains' events
-        launch_fd_build(stream, a, C, n, max_len, fd_ld, cold, max_new, grp->c_split[shard], grp->c_split[shard + 1]);
-    } else {
-        launch_fd_build(stream, a, C, n, max_len, fd_ld, cold, max_new);
-    }
-    kend(K_FD_BUILD, (double)(En - E0) * 2.0 * csz * n);
-    if (side_commit) HGX_TRY(hipStreamWaitEvent(stream, ev_side[1], 0));
-    if (rooted) {   // root floors of every position (after a Reset)
-        if (gfl.n < (size_t)Ppos) HGX_TRY(gfl.alloc((size_t)Ppos));
-        const size_t need = (size_t)(root_gmax + 1) * C;
-        if (gB.n < need) {
-            HGX_TRY(gB.alloc(need));
-            drop_step_graph();
-        }
-        launch_root_floor(stream, a, root_round_d.p, gfl.p, gB.p, root_gmax, C, n, max_len);
-    }
-    if (rebuild) {   // events received before the rebuild (a prefix of every chain)
-        HGX_TRY(hipMemsetAsync(fu.p, 0, (size_t)C * 4, stream));
-        launch_fu_count(stream, a, En);
-        h_fu.assign(C, 0);
-        HGX_TRY(hipMemcpyAsync(h_fu.data(), fu.p, (size_t)C * 4, hipMemcpyDeviceToHost, stream));
-    }
-    // a call resuming the state (not a rebuild) makes one host round trip: the wavefront's
-    // error flag is read with the rounds' results, and a lane that gave up (never seen in
-    // practice) redoes the call as a rebuild with the sweeps
-    const bool one_trip = !rebuild;
-    if (one_trip) {
-        HGX_TRY(hipEventRecord(ph2, stream));
-    } else {
-        HGX_TRY(hipEventRecord(ph1, stream));
-        HGX_TRY(hipEventSynchronize(ph1));
-        if (la_wave_used && h_small[48] != 0) {
-            // a wavefront lane gave up waiting (bounded spins): redo lastAncestors and the
-            // firstDescendants built from them with the sweeps
-            la_wave_used = false;
-            la_wave_fallbacks++;
-            HGX_TRY(hipMemsetAsync(LA.p, compact ? 0x00 : 0xFF, (size_t)h_off[C] * n * csz, stream));
-            HGX_TRY(run_sweeps(1));
-            launch_fd_build(stream, a, C, n, max_len, fd_ld, cold, max_new);
-            if (rooted) launch_root_floor(stream, a, root_round_d.p, gfl.p, gB.p, root_gmax, C, n, max_len);
-            HGX_TRY(hipEventRecord(ph1, stream));
-            HGX_TRY(hipEventSynchronize(ph1));
-        }
-        float ms = 0;
-        HGX_TRY(hipEventElapsedTime(&ms, ph0, ph1));
-        phase_ms[0] = ms;
-    }
-    h_len_div = chain_len;
-    E_div = En;
-    laid_out = true;
-
-    // rounds, step by step from r_lo
-    if (!one_trip) HGX_TRY(hipEventRecord(ph0, stream));
-    HGX_TRY(ensure_round_cap(r_lo + 2 * kStepBatch + 2));
-    a = arrays();
-    {   // one launch for the round tables' resets
-        FillRange fr[4] = {{lr.p, (uint32_t)((size_t)G * 4), 0xFF},
-                           {active.p + r_lo, (uint32_t)((size_t)(r_cap + 1 - r_lo) * 4), 0},
-                           {ovf.p + r_lo, (uint32_t)((size_t)(r_cap + 2 - r_lo) * 4), 0},
-                           {Bm.p, (uint32_t)((size_t)C * 4), 0}};
-        launch_fill_many(stream, fr, r_lo == 0 ? 4 : 3);
-        HGX_TRY(hipGetLastError());
-    }
-    {
-        const size_t need = (size_t)2 * C * round_k_ndw(n);
-        if (FD8.n < need) {
-            HGX_TRY(FD8.alloc(need));
-            drop_step_graph();
-        }
-    }
-    auto round_args = [&]() {
-        RoundArgs A{};
-        A.n = n; A.C = C; A.sm = sm; A.nw = nw; A.Pcap = fd_ld;
-        A.c_len = c_len.p; A.c_off = c_off.p; A.c_base = c_base.p; A.LA = LA.p; A.FDT = FDT.p; A.compact = compact;
-        A.p_gid = p_gid.p; A.g_coin = g_coin.p; A.FD8 = FD8.p; A.ovf = ovf.p;
-        A.Bm = Bm.p; A.WLA = WLA.p; A.WFD = WFD.p; A.p_round = p_round.p; A.active = active.p;
-        A.lr = lr.p; A.wflag = wflag.p; A.wstat = wstat.p; A.wcoin = wcoin.p; A.Smat = Smat.p;
-        A.gB = rooted ? gB.p : c_len.p;   // (any int array without roots: read, never used)
-        A.gmax = rooted ? root_gmax : -1;
-        return A;
-    };
-    // the tail of the call: every graph's last round over the rounds stepped so far, and the rows
-    // [r_lo, r_hi] of the boundaries / [r_lo, r_hi) of the witness flags for the host copies
-    // (rows beyond the last round are copied and dropped), then ph1
-    const int r_scan = rebuild ? 0 : r_lo;
-    const std::vector<int32_t> prev_last = out.last_round;
-    bool tail_ready = false, la_flag_read = false;
-    auto enqueue_tail = [&](int32_t r_hi) -> hipError_t {
-        stage_out.clear();   // (a tail queued before more steps were needed is superseded)
-        pend.clear();
-        stage_used = 0;
-        launch_last_round(stream, r_scan, r_hi, G, C, n, wstat.p, lr.p);
-        h_lr.assign(G, -1);
-        HGX_TRY(stage_d2h(h_lr.data(), lr.p, (size_t)G * 4));
-        const size_t b0 = (size_t)r_lo * C;
-        if (out.bm.size() < (size_t)(r_hi + 1) * C) out.bm.resize((size_t)(r_hi + 1) * C);
-        if (out.wflag.size() < (size_t)r_hi * C) out.wflag.resize((size_t)r_hi * C);
-        HGX_TRY(stage_d2h(out.bm.data() + b0, Bm.p + b0, ((size_t)(r_hi + 1) * C - b0) * 4));
-        if (r_hi > r_lo) HGX_TRY(stage_d2h(out.wflag.data() + b0, wstat.p + b0, (size_t)r_hi * C - b0));
-        if (one_trip && la_wave_used && !la_flag_read) {   // (read and re-armed once)
-            HGX_TRY(copy_to_pinned(h_small + 48, counters.p + 6, 4, 0));
-            la_flag_read = true;
-        }
-        HGX_TRY(stage_issue());
-        return hipEventRecord(ph1, stream);
-    };
-    kbeg(K_ROUND_GATHER);
-    launch_round_gather(stream, a, r_lo, C, n, fd_ld);   // W'_{r_lo}: round 0 = first event of every chain
-    kend(K_ROUND_GATHER, (double)C * n * 16);
-    int launched = 0, checked = 0;
-    // the persistent recurrence (hgx_round_p.hip): every round in one launch; r_done = rounds
-    // [r_lo, r_done) written (the last one empty)
-    int32_t r_done = -1;
-    auto run_persistent = [&]() -> hipError_t {
-        const int ndw = round_k_ndw(n);
-        if (FD8p.n < (size_t)kRoundPBufs * C * ndw) HGX_TRY(FD8p.alloc((size_t)kRoundPBufs * C * ndw));
-        if (rp_gran.n < (size_t)4 * C) HGX_TRY(rp_gran.alloc((size_t)4 * C));
-        if (rp_st.n < (size_t)4 + G) HGX_TRY(rp_st.alloc((size_t)4 + G));
-        int32_t* fin = rp_st.p + 4;
-        HGX_TRY(hipMemsetAsync(rp_gran.p, 0, (size_t)4 * C * 8, stream));   // no tag survives a call
-        HGX_TRY(hipMemsetAsync(fin, 0xFF, (size_t)G * 4, stream));          // no graph finished yet
-        // a chain-sharded group: this shard's chain block, its candidate rows and granules written into
-        // every shard's window; the host threads of the W shards meet at the barriers
-        const bool sh = grp && grp->W > 1;
-        int c_lo = 0, c_hi = C;
-        RoundPWindows win;
-        auto gwait = [&]() -> hipError_t { return grp->wait() ? hipSuccess : hipErrorUnknown; };
-        if (sh) {
-            c_lo = grp->c_split[shard];
-            c_hi = grp->c_split[shard + 1];
-            HGX_TRY(hipStreamSynchronize(stream));
-            HGX_TRY(gwait());   // every window is cleared and registered (its engine's FD8p / gran / st)
-            win.nwin = grp->W;
-            for (int k = 0; k <= grp->W; k++) win.c_split[k] = grp->c_split[k];
-            for (int k = 0; k < grp->W; k++) {
-                Engine* q = grp->eng[k];
-                win.FD8p[k] = q->FD8p.p;
-                win.gran[k] = q->rp_gran.p;
-                win.st[k] = q->rp_st.p;
-                win.FDT[k] = q->FDT.p;
-                if (grp->dev[k] != dev || (grp->force_remote && k != shard)) win.remote |= 1u << k;
-            }
-            if (rp_win.n < sizeof(RoundPWindows)) HGX_TRY(rp_win.alloc(sizeof(RoundPWindows)));
-            HGX_TRY(hipMemcpyAsync(rp_win.p, &win, sizeof(RoundPWindows), hipMemcpyHostToDevice, stream));
-            HGX_TRY(hipStreamSynchronize(stream));
-        }
-        const RoundPWindows* win_d = sh ? (const RoundPWindows*)rp_win.p : nullptr;
-        // n > 256 (one graph): k_round_pb, a workgroup per chain with events (hgx_round_pb.hip)
-        const bool big = n > 256;
-        int na = 0;
-        if (big) {
-            h_amap.clear();
-            for (int c = 0; c < C; c++)
-                if (chain_len[c] > 0) h_amap.push_back(c);
-            na = (int)h_amap.size();
-            if (na == 0) return hipErrorCooperativeLaunchTooLarge;   // (nothing to step: the steps' path)
-            if (rp_amap.n < (size_t)C) HGX_TRY(rp_amap.alloc((size_t)C));
-            HGX_TRY(hipMemcpyAsync(rp_amap.p, h_amap.data(), (size_t)na * 4, hipMemcpyHostToDevice, stream));
-        }
-        int32_t s = r_lo, last = -1;
-        int finished = 0;
-        for (int init = 1;; init = 0) {
-            if (r_cap - 1 <= s + 1) {
-                HGX_TRY(ensure_round_cap(s + 64));
-                a = arrays();
-            }
-            HGX_TRY(hipMemsetAsync(rp_st.p, 0, 16, stream));
-            if (big) {
-                kbeg(K_ROUND_SEARCH);
-                HGX_TRY(launch_round_pb(stream, round_args(), FD8p.p, rp_gran.p, rp_st.p, fin, rp_amap.p, na, s, r_cap - 1,
-                                        num_cus, init != 0));
-                kend(K_ROUND_SEARCH, 0);
-            } else if (sh && init) {
-                // W'_{r_lo} of this shard's chains into every window; every shard's launch starts once
-                // every window holds the whole W'_{r_lo}
-                HGX_TRY(launch_round_p(stream, round_args(), FD8p.p, rp_gran.p, rp_st.p, fin, s, r_cap - 1, 2, num_cus,
-                                       c_lo, c_hi, win_d, win.nwin));
-                HGX_TRY(hipStreamSynchronize(stream));
-                HGX_TRY(gwait());
-            }
-            if (!big) {
-                kbeg(K_ROUND_SEARCH);
-                HGX_TRY(launch_round_p(stream, round_args(), FD8p.p, rp_gran.p, rp_st.p, fin, s, r_cap - 1, sh ? 0 : init,
-                                       num_cus, c_lo, c_hi, win_d, sh ? win.nwin : 1));
-                kend(K_ROUND_SEARCH, 0);
-            }
-            HGX_TRY(hipMemcpyAsync(h_small + 56, rp_st.p, 16, hipMemcpyDeviceToHost, stream));
-            HGX_TRY(hipStreamSynchronize(stream));
-            round_p_runs++;
-            round_p_ovf += h_small[59];
-            int32_t st0 = h_small[56], st1 = h_small[57], st2 = h_small[58], st3 = h_small[59];
-            if (sh) {
-                // every shard's outcome; then this shard's round rows into every shard's tables
-                for (int k = 0; k < 4; k++) grp->st[shard][k] = h_small[56 + k];
-                HGX_TRY(gwait());
-                for (int k = 0; k < grp->W; k++) {
-                    if (grp->st[k][0] != 0 && st0 == 0) {
-                        st0 = grp->st[k][0];
-                        st3 = grp->st[k][3];
-                    }
-                    st1 = std::max(st1, grp->st[k][1]);
-                    st2 = std::max(st2, grp->st[k][2]);
-                }
-                if (st0 == 0) HGX_TRY(share_round_rows(s, std::min(st1 + 1, r_cap)));
-                HGX_TRY(gwait());
-            }
-            if (st0 != 0) {   // a workgroup gave up waiting: st[0] = 1 + its chain, st[3] its round
-                round_p_fail_chain = st0 - 1;
-                round_p_fail_round = st3;
-                return hipErrorLaunchTimeOut;
-            }
-            last = std::max(last, st1);
-            finished += st2;
-            if (finished >= G) {
-                r_done = last + 1;
-                // graphs that finished earlier: empty rows up to the last round (k_last_round,
-                // fame and the host copies read every graph's rows of every round)
-                launch_round_p_tail(stream, round_args(), fin, last);
-                if (big) launch_round_pb_silent(stream, round_args(), r_lo, last);
-                kbeg(K_ROUND_GATHER);
-                launch_round_p_post(stream, round_args(), r_lo, last);
-                kend(K_ROUND_GATHER, (double)(last - r_lo + 1) * C * n * (sizeof(int32_t) + (compact ? 2 : 4)));
-                return hipGetLastError();
-            }
-            s = st1;   // the round tables' capacity: continue from there
-        }
-    };
-    // the whole-graph recurrence (hgx_round_g.hip, n <= 16): one workgroup per graph, every round
-    // in one launch, nothing shared between workgroups; relaunched from the round tables'
-    // capacity (its prologue rebuilds a round's state from Bm alone)
-    auto run_graph = [&]() -> hipError_t {
-        if (rp_st.n < (size_t)4 + G) HGX_TRY(rp_st.alloc((size_t)4 + G));
-        int32_t* fin = rp_st.p + 4;
-        HGX_TRY(hipMemsetAsync(fin, 0xFF, (size_t)G * 4, stream));
-        int32_t s = r_lo, last = -1;
-        int finished = 0;
-        for (;;) {
-            if (r_cap - 1 <= s + 1) {
-                HGX_TRY(ensure_round_cap(s + 64));
-                a = arrays();
-            }
-            HGX_TRY(hipMemsetAsync(rp_st.p, 0, 16, stream));
-            kbeg(K_ROUND_SEARCH);
-            HGX_TRY(launch_round_g(stream, round_args(), rp_st.p, fin, s, r_cap - 1));
-            kend(K_ROUND_SEARCH, 0);
-            HGX_TRY(hipMemcpyAsync(h_small + 56, rp_st.p, 16, hipMemcpyDeviceToHost, stream));
-            HGX_TRY(hipStreamSynchronize(stream));
-            round_g_runs++;
-            round_p_ovf += h_small[59];
-            last = std::max(last, h_small[57]);
-            finished += h_small[58];
-            if (finished >= G) {
-                r_done = last + 1;
-                launch_round_p_tail(stream, round_args(), fin, last);
-                kbeg(K_ROUND_GATHER);
-                launch_round_p_post(stream, round_args(), r_lo, last);
-                kend(K_ROUND_GATHER, (double)(last - r_lo + 1) * C * n * (sizeof(int32_t) + (compact ? 2 : 4)));
-                return hipGetLastError();
-            }
-            s = h_small[57];   // the round tables' capacity: continue from there
-        }
-    };
-    const bool graph_ok = !rooted && round_g_ok(n, nw) && (round_kernel == 0 || round_kernel == 4) && !grp;
-    if (graph_ok) HGX_TRY(run_graph());
-    // the persistent launch pays a fixed cost (every chain's window staged, 256 resident
-    // workgroups) that a call resuming for a few rounds does not recover: those use the steps
-    // (a chain-sharded group always runs it: its shards build firstDescendants for their own chains only)
-    if (!graph_ok && !rooted && (round_kernel == 3 || (round_kernel == 0 && rebuild) || grp) &&
-        (round_p_ok(n, C, num_cus) || (round_pb_ok(n, G) && !grp && round_pb_enabled))) {
-        const hipError_t pe = run_persistent();
-        if (pe != hipSuccess) {
-            // redo the rounds with the per-launch steps (a timed-out launch left partial rows)
-            (void)hipGetLastError();
-            if (pe != hipErrorLaunchTimeOut && pe != hipErrorCooperativeLaunchTooLarge) return pe;
-            round_p_fallbacks++;
-            r_done = -1;
-            if (grp) {
-                // the steps read every candidate's firstDescendants: this shard built its own chains'
-                // only, so the whole table is rebuilt here, and W'_{r_lo} gathered again from it
-                launch_fd_build(stream, a, C, n, max_len, fd_ld, nullptr, 0);
-                launch_round_gather(stream, a, r_lo, C, n, fd_ld);
-            }
-        }
-    }
-    if (r_done >= 0 && rebuild && !graph_ok && !rooted && round_kernel == 0) {
-        // the resumed calls that follow use the per-launch steps: their hipGraphs are captured and
-        // instantiated now, inside this (long) rebuild call, not in the first short resumed one
-        // (c2: a 7 ms first resumed call)
-        for (int i = 1; i <= 2; i++)
-            if (!step_g[i].exec) HGX_TRY(capture_steps(step_g[i], round_args(), 0, i == 1 ? kStepBatchSmall : 2 * kStepBatchSmall));
-    }
-    if (r_done < 0) launch_round_k_gather(stream, round_args(), r_lo);   // W'_{r_lo} rebased for k_round_k
-    // a rebuild replays kStepBatch steps per hipGraph; a resumed call (a few rounds) 2 or 4: a
-    // round holds ~10-14 events per chain, so fewer than 6 new events per chain rarely take
-    // more than two steps (a second batch costs another host round trip)
-    const bool few = (En - E0) < 6 * (int64_t)C;
-    StepGraph& sgr = step_g[rebuild ? 0 : few ? 1 : 2];
-    const int nb = rebuild ? kStepBatch : few ? kStepBatchSmall : 2 * kStepBatchSmall;
-    if (r_done < 0) {   // n <= 1024 (hgx_create's limit)
-        // nb step nodes replayed as one hipGraph; before each replay the nodes' round
-        // arguments are rewritten (hipGraphExecKernelNodeSetParams), so a step knows its
-        // round without a dependent device load. Batch i+1 is queued before the host looks
-        // at batch i's "any candidate left" flag (pipelined check).
-        auto launch_batch = [&]() -> hipError_t {
-            const int need = r_lo + (launched + 2) * nb + 2;
-            if (need > r_cap) {
-                HGX_TRY(ensure_round_cap(need));
-                a = arrays();
-            }
-            const int kern = (rooted || round_kernel != 1) ? 0 : 1;   // root floors: per-candidate step only
-            const RoundArgs cur = round_args();
-            if (!sgr.exec || sgr.kernel != kern || sgr.compact != compact || sgr.nb != nb || sgr.args.gB != cur.gB ||
-                sgr.args.gmax != cur.gmax)
-                HGX_TRY(capture_steps(sgr, cur, kern, nb));
-            const int slot = launched & 1;
-            // the batch's last step writes round + 1 into this slot's host-mapped flag when a
-            // chain still has events beyond its boundary (no D2H copy between the replays)
-            sgr.args_last[slot] = sgr.args;
-            sgr.args_last[slot].hflag = d_flag + slot;
-            h_flag[slot] = 0;
-            for (int k = 0; k < nb; k++) {
-                sgr.round[k] = r_lo + launched * nb + k;
-                void* args[2] = {(void*)(k == nb - 1 ? &sgr.args_last[slot] : &sgr.args), (void*)&sgr.round[k]};
-                hipKernelNodeParams kp = sgr.params[k];
-                kp.kernelParams = args;
-                kp.extra = nullptr;
-                HGX_TRY(hipGraphExecKernelNodeSetParams(sgr.exec, sgr.nodes[k], &kp));
-            }
-            // nb step kernels per replay, every replay bracketed by timing events when the round
-            // search is timed (a sample of replays misjudged the pass: the first replays' rounds hold
-            // most of the events, the last ones' steps find little left -- c5: 19.4 ms sampled
-            // against 12.8 ms in the rocprofv3 trace)
-            const bool sample = true;
-            kbeg(K_ROUND_SEARCH, sample, nb);
-            HGX_TRY(hipGraphLaunch(sgr.exec, stream));
-            if (sample) kend(K_ROUND_SEARCH, 0);
-            HGX_TRY(hipEventRecord(flag_ev[slot], stream));
-            launched++;
-            return hipSuccess;
-        };
-        // a rebuild keeps two batches in flight; a resumed call usually ends within its first
-        // batch, so it waits for that batch's flag before queueing another
-        HGX_TRY(launch_batch());
-        if (rebuild) HGX_TRY(launch_batch());
-        if (one_trip) {
-            // the tail queued right behind the first batch: when that batch ends the rounds (the
-            // usual resumed call), the call has made its only host round trip here
-            HGX_TRY(enqueue_tail(r_lo + launched * nb));
-            HGX_TRY(hipEventSynchronize(ph1));
-            const int more = __atomic_load_n(&h_flag[0], __ATOMIC_ACQUIRE);
-            checked = 1;
-            if (!more) tail_ready = true;
-            else {
-                if (launched == checked) HGX_TRY(launch_batch());
-                HGX_TRY(launch_batch());
-            }
-        }
-        while (!tail_ready) {
-            HGX_TRY(hipEventSynchronize(flag_ev[checked & 1]));
-            const int more = __atomic_load_n(&h_flag[checked & 1], __ATOMIC_ACQUIRE);
-            checked++;
-            if (!more) break;
-            if (launched == checked) HGX_TRY(launch_batch());   // no batch in flight
-            HGX_TRY(launch_batch());
-        }
-    }
-    if (!tail_ready) {
-        HGX_TRY(enqueue_tail(r_done >= 0 ? r_done : r_lo + launched * nb));
-        HGX_TRY(hipEventSynchronize(ph1));
-    }
-    if (one_trip && la_wave_used && h_small[48] != 0) {
-        // a wavefront lane gave up waiting (bounded spins): the call again as a rebuild, with
-        // the sweeps for lastAncestors
-        la_wave_fallbacks++;
-        laid_out = false;
-        stage_out.clear();
-        const int keep = la_kernel;
-        la_kernel = 1;
-        const hipError_t re = divide_rounds(En, chain_len, chain_base, out);
-        la_kernel = keep;
-        return re;
-    }
-    // the staged rows: the graphs' last rounds (the first entry) are needed now; the boundary and
-    // witness-flag rows (megabytes at c3) can wait for divide_rounds_rows when the caller asked so
-    const bool defer = defer_rows && !stage_out.empty();
-    defer_rows = false;
-    if (defer) {
-        StagedD2H& d = stage_out[0];
-        std::memcpy(d.dst, h_stage + d.off, d.bytes);
-        d.bytes = 0;
-    } else {
-        stage_flush();
-    }
-    // rounds below r_lo are unchanged and every round up to a graph's last one has witnesses,
-    // so only [r_lo, R) is scanned: last = max(that, min(previous last, r_lo - 1))
-    if (r_scan > 0)
-        for (int g = 0; g < G; g++) {
-            const int32_t pl = g < (int)prev_last.size() ? prev_last[g] : -1;
-            h_lr[g] = std::max(h_lr[g], std::min(pl, r_scan - 1));
-        }
-    out.last_round.assign(h_lr.begin(), h_lr.end());
-    int32_t mx = -1;
-    for (int g = 0; g < G; g++) mx = std::max(mx, out.last_round[g]);
-    R = mx + 1;
-    out.R = R;
-    out.r_lo = std::min(r_lo, R);
-    // the host copies keep the rows below r_lo (rows the tail copied beyond R are dropped)
-    rows_pending = defer;
-    rows_n = stage_out.size();
-    if (!defer) {
-        out.bm.resize((size_t)(R + 1) * C);
-        out.wflag.resize((size_t)R * C);
-    }
-    launch_wcoin(stream, a, out.r_lo, R, C);   // (DecideFame reads the coins on this stream)
-    HGX_TRY(hipGetLastError());
-    float ms = 0;
-    if (one_trip) {
-        HGX_TRY(hipEventElapsedTime(&ms, ph0, ph2));
-        phase_ms[0] = ms;
-        HGX_TRY(hipEventElapsedTime(&ms, ph2, ph1));
-    } else {
-        HGX_TRY(hipEventElapsedTime(&ms, ph0, ph1));
-    }
-    phase_ms[1] = ms;
-    step_prof_dump();   // -DHGX_STEP_PROF builds only
-    return collect_kernel_times();
 }
 
 // the rows divide_rounds left in the staging (defer_rows): copied into the host tables, which get
@@ -2216,20 +1508,20 @@ hipError_t Engine::find_order_begin(const std::vector<uint8_t>& el, const std::v
     launch_threshold(stream, a, r0, R, C, n);
     kend(K_THRESHOLD, 0);
     {
-        FillRange fr[2] = {{counters.p, 8, 0}, {rcnt.p, (uint32_t)((size_t)C * 4), 0}};
+        FillRange fr[2] = {{counters.p + kCtRecv, 8, 0}, {rcnt.p, (uint32_t)((size_t)C * 4), 0}};
         launch_fill_many(stream, fr, 2);
         HGX_TRY(hipGetLastError());
     }
     kbeg(K_ROUND_RECEIVED);
     launch_round_received(stream, a, R, C, n, max_unrecv);
     kend(K_ROUND_RECEIVED, 0);
-    HGX_TRY(copy_to_pinned(h_small, counters.p, 8));
+    HGX_TRY(copy_to_pinned(h_small + kHsRecv, counters.p + kCtRecv, 8));
     HGX_TRY(stage_d2h(fo_cnt.data(), rcnt.p, (size_t)C * 4));
     HGX_TRY(stage_issue());
     HGX_TRY(hipStreamSynchronize(stream));
     stage_flush();
-    fo_m = h_small[0];
-    out.panic = h_small[1] != 0;
+    fo_m = h_small[kHsRecv];
+    out.panic = h_small[kHsRecv + 1] != 0;
     out.m = fo_m;
     int max_cnt = 0, unrecv = 0;
     for (int c = 0; c < C; c++) unrecv += h_len_div[c] - h_fu[c];

@@ -12,14 +12,20 @@
 #include <thread>
 #include <vector>
 
+#include "hgx_divide_plan.h"
 #include "hgx_ingest_cols.h"
 #include "hgx_kernels.h"
 
+#ifndef HGX_TRY
+#define HGX_TRY(x)                              \
+    do {                                        \
+        hipError_t _e = (x);                    \
+        if (_e != hipSuccess) return _e;        \
+    } while (0)
+#endif
+
 namespace hgx {
 
-
-constexpr int kStepBatch = 16;        // round steps per hipGraph replay (a full DivideRounds)
-constexpr int kStepBatchSmall = 2;    // ... when resuming at the lowest changed round
 
 // kStepBatch round steps captured as one hipGraph, replayed with rewritten round arguments
 struct StepGraph {
@@ -434,7 +440,6 @@ class Engine {
                                  const uint8_t* op_id32, uint8_t* out_id32, InsertOut& out, const WireRun* wire);
     hipStream_t stream2 = nullptr;   // payload copies of insert_split (created on first use)
     // the pipelined ingest: stream_p and stream_o take the pieces' k_la_wave launches in turn
-    void layout_slots(int64_t En, const std::vector<int32_t>& chain_len, std::vector<int32_t>& off) const;
     int rebuild_segments(int64_t En, int coord_compact) const;
     hipStream_t stream_p = nullptr;
     hipEvent_t ev_pc[kPipeMaxPieces + 1] = {}, ev_lay[kPipeMaxPieces] = {}, ev_side[2] = {};
@@ -555,6 +560,69 @@ class Engine {
     hipEvent_t la_ev[kLaRing] = {};
     StepGraph step_g[3];   // [0] full DivideRounds, [1] / [2] resumed (incremental) calls of 2 / 4 steps
     void drop_step_graph();
+    // The words of `counters` (device) and of h_small (pinned, where the host reads results), in ints.
+    // A sweep's ring slot holds 4 ints: rows recomputed, units changed, two spare.
+    static constexpr int kCtRecv = 0;       // FindOrder: events received, [+1] the panic flag
+    static constexpr int kCtWaveErr = 6;    // a k_la_wave / k_la_small lane gave up
+    static constexpr int kCtSweep = 8;      // the sweeps' ring [kLaRing][4]
+    static constexpr int kCtWords = kCtSweep + 4 * kLaRing;
+    static constexpr int kHsInsFail = 0;    // insert: the first-failure word (8 bytes)
+    static constexpr int kHsInsFailSig = 2; // ... and the signatures' (8 bytes)
+    static constexpr int kHsRecv = 0;       // FindOrder's received / panic pair, in the insert's words: every
+                                            // call reads its own before it returns, and calls do not overlap
+    static constexpr int kHsSweep = 16;     // the sweeps' ring [kLaRing][4] (rows and changed are copied)
+    static constexpr int kHsWaveErr = kHsSweep + 4 * kLaRing;
+    static constexpr int kHsSegCheck = 50;  // the time segments' exactness check
+    static constexpr int kHsRoundSt = 56;   // the four status words of a recurrence launch
+    static constexpr int kHsWords = 64;
+    static_assert(kCtRecv + 2 <= kCtWaveErr && kCtWaveErr < kCtSweep, "counters: ranges overlap");
+    static_assert(kHsInsFail + 2 <= kHsInsFailSig && kHsInsFailSig + 2 <= kHsSweep && kHsRecv + 2 <= kHsSweep,
+                  "h_small: the insert's / FindOrder's words reach the sweep ring");
+    static_assert(kHsWaveErr < kHsSegCheck && kHsSegCheck < kHsRoundSt && kHsRoundSt + 4 <= kHsWords,
+                  "h_small: ranges overlap or leave the block");
+
+    // ---- DivideRounds (hgx_engine_divide.cpp): divide_rounds runs these phases in order; they share the
+    // call's state through one DivCall on its stack
+    struct DivCall {
+        int64_t En;
+        const std::vector<int32_t>&chain_len, &chain_base;
+        RoundsHost& out;
+        const DividePlan& plan;
+        bool sweeps_only;              // the second attempt: lastAncestors by the sweeps
+        DevArrays a{};                 // re-taken by whoever grows a table
+        const int32_t* cold = nullptr; // the chains' old lengths (device) on a resumed call
+        const int32_t* la_map = nullptr;
+        bool piped = false;            // the pipelined ingest laid out and ran the segments' main pass
+        bool side_commit = false;      // the payload's commit is in flight on the side stream
+        RoundChoice rc{};
+        int32_t r_done = -1;           // a recurrence wrote rounds [r_lo, r_done) (the last one empty)
+        int launched = 0, checked = 0; // step batches queued / whose flag the host has read
+        bool tail_ready = false;       // the tail queued behind the first batch stands
+        bool la_flag_read = false;     // the wavefront's error word is queued with the tail (once)
+        bool one_trip() const { return !plan.rebuild; }
+        int32_t r_scan() const { return plan.rebuild ? 0 : plan.r_lo; }
+    };
+    DividePlan div_plan;   // (its lane map keeps its capacity over the calls)
+    hipError_t divide_attempt(DivCall& d);
+    hipError_t div_layout(DivCall& d);
+    hipError_t div_last_ancestors(DivCall& d);
+    hipError_t div_coordinates(DivCall& d);
+    hipError_t run_sweeps(DivCall& d, int first_mode);
+    hipError_t fd_then_floors(DivCall& d, const int32_t* cold, int max_new, int d_lo, int d_hi, bool floors, bool timed);
+    hipError_t div_rebuild_wait(DivCall& d);
+    hipError_t div_round_tables(DivCall& d);
+    RoundArgs round_args() const;
+    enum RecurKind { kRecurGraph, kRecurPersistent };
+    struct PersistentSetup;
+    hipError_t persistent_setup(DivCall& d, PersistentSetup& ps);
+    hipError_t persistent_launch(const PersistentSetup& ps, int32_t* fin, int32_t s, int init);
+    hipError_t persistent_share(int32_t s, int32_t st[4]);
+    hipError_t run_recurrence(DivCall& d, RecurKind kind);
+    hipError_t div_recurrence(DivCall& d);
+    hipError_t launch_batch(DivCall& d);
+    hipError_t div_steps(DivCall& d);
+    hipError_t enqueue_tail(DivCall& d, int32_t r_hi);
+    hipError_t div_finish(DivCall& d);
     DBuf<uint8_t> wflag, wstat, wcoin, elig, fw, ur_empty;
     DBuf<uint64_t> Smat, Vbuf;
     DBuf<uint32_t> FD8;   // [2][C][ndw] rebased candidate rows (k_round_k)
@@ -567,7 +635,6 @@ class Engine {
     DBuf<uint8_t> rp_win;     // a chain-sharded group's RoundPWindows (device copy read by k_round_p)
     DBuf<int32_t> la_lmap;          // k_la_wave lanes -> chains with events (one graph, n > 896)
     DBuf<int32_t> la_chk;           // k_la_seg_check: [0] flag, then the segments' first rows [(nts + 1) x n]
-    std::vector<int32_t> h_lmap;
     DBuf<int32_t> ovf;    // [r_cap + 2]
     DBuf<int8_t> fame;
     // order

@@ -45,7 +45,9 @@ struct DevArrays {
     int32_t* recv_list;
     int32_t *fu, *rcnt;   // [C] per chain: events received by earlier calls (a prefix) / by this call
     uint32_t* scan_part;  // scan partials
-    int32_t* counters;   // [0] received count, [1] panic flag, [2] LA changed
+    int32_t* counters;   // [0] received count, [1] panic flag (FindOrder); the host passes [6] (a lastAncestors
+                         // wavefront lane gave up) and [8 ..) (the sweeps' ring: rows, units changed per slot) to
+                         // their kernels as pointers (Engine::kCt*, hgx_engine.h)
     // order
     uint64_t *key_a, *key_b;
     uint32_t *val_a, *val_b;
