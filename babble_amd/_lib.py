@@ -153,6 +153,10 @@ def lib():
         _sig(L, nm, i32, [p, C.POINTER(hgx_events), p, p, i64, C.POINTER(C.c_int64), E])
     _sig(L, "hgx_insert_event_bodies", i32, [p, C.POINTER(hgx_event_bodies), i64, p, C.POINTER(C.c_int64), E])
     _sig(L, "hgx_insert_event_bodies_ext", i32, [p, C.POINTER(hgx_event_bodies), p, i64, p, C.POINTER(C.c_int64), E])
+    _sig(L, "hgx_set_signing_keys", i32, [p, p, E])
+    _sig(L, "hgx_sign_insert_event_bodies", i32, [p, C.POINTER(hgx_event_bodies), p, i64, p, p, p, C.POINTER(C.c_int64), E])
+    _sig(L, "hgx_p256_sign_batch", i32, [i32, p, i32, p, p, i64, p, p, E])
+    _sig(L, "hgx_p256_public_keys", i32, [i32, p, i32, p, E])
     _sig(L, "hgx_event_json_batch", i32, [i32, C.POINTER(hgx_event_bodies), i64, p, i32, p, p, p, i64, p, E])
     _sig(L, "hgx_batch_levels", i32, [p, p, i64, i64, p, C.POINTER(C.c_int32), E])
     _sig(L, "hgx_reset_consensus", i32, [p])

@@ -863,9 +863,13 @@ int32_t hgx_insert_events_verified_device(hgx_ctx* c, const hgx_events* ev, cons
 // gid) cuts the batch: the prefix goes through the body path, then that event through the plain insert
 // checks, which reject it with the reference's parent-check error. On a context with root ids
 //  self-parent -1, HGX_ROOT_Y and HGX_ROOT_OTHER print the roots' ids.
-int32_t hgx_insert_event_bodies_ext(hgx_ctx* c, const hgx_event_bodies* evb, const uint8_t* other_parent_id32,
-                                    int64_t count, uint8_t* out_id32, int64_t* n_inserted, hgx_error* err) {
-    const std::string who = "hgx_insert_event_bodies: ";
+// sign (hgx_sign_insert_event_bodies): R and S come from the device (evb's are not read),
+// out_r32 / out_s32 get the accepted prefix's; everything else is the same call.
+static int32_t insert_event_bodies_impl(hgx_ctx* c, const hgx_event_bodies* evb, const uint8_t* other_parent_id32,
+                                        int64_t count, bool sign, uint8_t* out_r32, uint8_t* out_s32, uint8_t* out_id32,
+                                        int64_t* n_inserted, hgx_error* err) {
+    const char* fn = sign ? "hgx_sign_insert_event_bodies" : "hgx_insert_event_bodies";
+    const std::string who = std::string(fn) + ": ";
     auto bad = [&](const std::string& why) {
         set_err(err, HGX_ERR_INVALID, who + why);
         return (int32_t)HGX_ERR_INVALID;
@@ -873,22 +877,31 @@ int32_t hgx_insert_event_bodies_ext(hgx_ctx* c, const hgx_event_bodies* evb, con
     if (n_inserted) *n_inserted = 0;
     if (!evb || count < 0) return bad("bad arguments");
     const hgx::BodiesIn ev{evb->creator, evb->index, evb->self_parent, evb->other_parent, evb->timestamp_ns,
-                           evb->sig_r, evb->sig_s, evb->ntx, evb->tx_off, evb->tx_bytes};
+                           sign ? nullptr : evb->sig_r, sign ? nullptr : evb->sig_s, evb->ntx, evb->tx_off, evb->tx_bytes};
     std::vector<int64_t> txi;
-    if (const char* why = hgx::bodies_check(ev, count, txi)) return bad(why);
+    if (const char* why = hgx::bodies_check(ev, count, txi, !sign)) return bad(why);
     if (!c) return bad("bad arguments");
     if (c->grp) return bad("not available on a chain-sharded context");
     if (c->shard_world > 1) return bad("not available on a row-sharded context");
     if (c->rooted && !c->root_ids_known) return bad("not after hgx_reset without root ids (hgx_set_root_ids)");
     if (!c->eng.keys_set) return bad("participant keys not set");
     if (!c->eng.ids_known) return bad("ids not known (the context holds events inserted without their ids)");
+    if (sign) {
+        if (!c->eng.sign_keys_set) return bad("signing keys not set");
+        for (int64_t k = 0; k < count; k++) {
+            const int32_t cr = ev.creator[k];
+            if (cr >= 0 && cr < c->C && !c->eng.sign_has[(size_t)cr])
+                return bad("event " + std::to_string(k) + ": creator " + std::to_string(cr) + " has no signing key");
+        }
+    }
     DeviceGuard dg(c);
     const bool root_ids = c->eng.root_ids_set;   // else the codes below -1 have no text, as on an unrooted context
     const int64_t cut = hgx::bodies_first_unencodable(ev, count, c->E, c->C, root_ids ? c->root_has_y.data() : nullptr,
                                                       other_parent_id32 != nullptr);
     hgx::InsertOut out;
-    hipError_t e = c->eng.insert_bodies(ev, txi, cut, other_parent_id32, out_id32, out);
-    if (e != hipSuccess) return dev_err(err, e, "hgx_insert_event_bodies");
+    hipError_t e = sign ? c->eng.sign_insert_bodies(ev, txi, cut, other_parent_id32, out_r32, out_s32, out_id32, out)
+                        : c->eng.insert_bodies(ev, txi, cut, other_parent_id32, out_id32, out);
+    if (e != hipSuccess) return dev_err(err, e, fn);
     if (out.code == hgx::INS_OK && cut < count) {
         // the cut event's own checks (it cannot pass them: its creator or a parent is unknown)
         const int64_t ok_before = out.accepted;
@@ -896,14 +909,56 @@ int32_t hgx_insert_event_bodies_ext(hgx_ctx* c, const hgx_event_bodies* evb, con
         const int32_t ntx = evb->ntx[cut] < 0 ? 0 : evb->ntx[cut], nil = evb->ntx[cut] < 0 ? 1 : 0;
         hgx::InsertIn in{};
         e = c->eng.stage(wide_cols(ev.creator + cut, ev.index + cut, ev.sp + cut, ev.op + cut, ev.ts + cut, zero,
-                                   ev.s + 32 * cut, &ntx, &nil),
+                                   sign ? zero : ev.s + 32 * cut, &ntx, &nil),
                          1, hgx::Engine::kStageAll, in);
         if (e == hipSuccess) e = c->eng.insert(in, 1, out);
-        if (e != hipSuccess) return dev_err(err, e, "hgx_insert_event_bodies");
+        if (e != hipSuccess) return dev_err(err, e, fn);
         if (out.code == hgx::INS_OK) c->eng.ids_known = false;   // (unreachable: the event was stored without an id)
         out.accepted += ok_before;
     }
     return finish_insert(c, out, n_inserted, err);
+}
+
+int32_t hgx_insert_event_bodies_ext(hgx_ctx* c, const hgx_event_bodies* evb, const uint8_t* other_parent_id32,
+                                    int64_t count, uint8_t* out_id32, int64_t* n_inserted, hgx_error* err) {
+    return insert_event_bodies_impl(c, evb, other_parent_id32, count, false, nullptr, nullptr, out_id32, n_inserted, err);
+}
+
+// Core.SignAndInsertSelfEvent / Core.AddSelfEvent (node/core.go:122-130, 232-255) for a batch
+int32_t hgx_sign_insert_event_bodies(hgx_ctx* c, const hgx_event_bodies* evb, const uint8_t* other_parent_id32,
+                                     int64_t count, uint8_t* out_r32, uint8_t* out_s32, uint8_t* out_id32,
+                                     int64_t* n_inserted, hgx_error* err) {
+    return insert_event_bodies_impl(c, evb, other_parent_id32, count, true, out_r32, out_s32, out_id32, n_inserted, err);
+}
+
+// The private keys Event.Sign uses on this context: C rows of 32 big-endian bytes, all
+// zero = the participant does not sign here, NULL clears. Every other row must be in [1, N-1] and its
+// d G the participant's key.
+int32_t hgx_set_signing_keys(hgx_ctx* c, const uint8_t* priv32, hgx_error* err) {
+    auto bad = [&](const std::string& why) {
+        set_err(err, HGX_ERR_INVALID, "hgx_set_signing_keys: " + why);
+        return (int32_t)HGX_ERR_INVALID;
+    };
+    if (!c) return bad("bad arguments");
+    if (c->grp) return bad("not available on a chain-sharded context");
+    if (c->shard_world > 1) return bad("not available on a row-sharded context");
+    DeviceGuard dg(c);
+    if (priv32) {
+        if (!c->eng.keys_set) return bad("participant keys not set");
+        static const uint8_t zero[32] = {};
+        for (int32_t k = 0; k < c->C; k++) {
+            const uint8_t* d = priv32 + 32 * (size_t)k;
+            if (std::memcmp(d, zero, 32) != 0 && !hgx::p256_scalar_ok(d))
+                return bad("key " + std::to_string(k) + " is not below N");
+        }
+    }
+    int32_t mismatch = -1;
+    const hipError_t e = c->eng.set_signing_keys(priv32, &mismatch);
+    if (e != hipSuccess) return dev_err(err, e, "hgx_set_signing_keys");
+    if (mismatch >= 0)
+        return bad("key " + std::to_string(mismatch) + " does not match participant " + std::to_string(mismatch) +
+                   "'s public key");
+    return ok(err);
 }
 
 int32_t hgx_insert_event_bodies(hgx_ctx* c, const hgx_event_bodies* evb, int64_t count, uint8_t* out_id32,

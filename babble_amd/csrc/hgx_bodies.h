@@ -24,8 +24,9 @@ constexpr int64_t kBodyChunkBytes = 32ll << 20;    // JSON bytes per internal ch
 constexpr int64_t kBodyFixedBytes = 576;           // bound of an event's JSON without its transactions, padded
 
 // nullptr if the columns are usable, else what is wrong with them. txi (count + 1 entries) gets each
-// event's first entry of tx_off (the running sum of max(ntx, 0)).
-const char* bodies_check(const BodiesIn& ev, int64_t count, std::vector<int64_t>& txi);
+// event's first entry of tx_off (the running sum of max(ntx, 0)). need_sig = false: the r and s columns
+// may be null (the signing path, where the device computes both).
+const char* bodies_check(const BodiesIn& ev, int64_t count, std::vector<int64_t>& txi, bool need_sig = true);
 
 // An event's depth inside the batch whose first event has gid `base`: 0 when no parent has gid >=
 // base, else 1 + the maximum over its in-batch parents. Returns -1, or the position of the first

@@ -8,10 +8,10 @@
 
 namespace hgx {
 
-const char* bodies_check(const BodiesIn& ev, int64_t count, std::vector<int64_t>& txi) {
+const char* bodies_check(const BodiesIn& ev, int64_t count, std::vector<int64_t>& txi, bool need_sig) {
     txi.assign((size_t)(count > 0 ? count : 0) + 1, 0);
     if (count <= 0) return nullptr;
-    if (!ev.creator || !ev.index || !ev.sp || !ev.op || !ev.ts || !ev.r || !ev.s || !ev.ntx || !ev.tx_off)
+    if (!ev.creator || !ev.index || !ev.sp || !ev.op || !ev.ts || (need_sig && (!ev.r || !ev.s)) || !ev.ntx || !ev.tx_off)
         return "null column";
     int64_t t = 0;
     for (int64_t k = 0; k < count; k++) {

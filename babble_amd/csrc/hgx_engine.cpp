@@ -115,6 +115,7 @@ hipError_t Engine::share_round_rows(int32_t r_a, int32_t r_b) {
 }
 
 Engine::~Engine() {
+    if (stream) (void)wipe_signing_keys();   // the private keys' HBM copy is zeroed before it is freed
     free_ev_scratch(ev_scratch);
     if (pay_thread.joinable()) pay_thread.join();
     if (stream2) (void)hipStreamSynchronize(stream2);
@@ -601,6 +602,60 @@ hipError_t Engine::set_keys(const uint8_t* keys65) {
     HGX_TRY(hipGetLastError());
     HGX_TRY(hipStreamSynchronize(stream));
     keys_set = true;
+    return wipe_signing_keys();   // (signing keys were checked against the keys this call replaced)
+}
+
+hipError_t Engine::wipe_signing_keys() {
+    sign_keys_set = false;
+    sign_has.clear();
+    if (sk_keys.p) {
+        HGX_TRY(hipMemsetAsync(sk_keys.p, 0, sk_keys.n, stream));
+        HGX_TRY(hipStreamSynchronize(stream));
+        sk_keys.release();
+    }
+    return hipSuccess;
+}
+
+hipError_t Engine::set_signing_keys(const uint8_t* priv32, int32_t* mismatch) {
+    *mismatch = -1;
+    if (!priv32) return wipe_signing_keys();
+    if (!keys_set) return hipErrorNotReady;
+    const size_t nc = (size_t)C;
+    DBuf<uint8_t> fresh, pub;
+    struct Wipe {   // the candidate copy never outlives this call unzeroed
+        DBuf<uint8_t>& b;
+        hipStream_t s;
+        ~Wipe() {
+            if (!b.p) return;
+            (void)hipMemsetAsync(b.p, 0, b.n, s);
+            (void)hipStreamSynchronize(s);
+        }
+    } wipe{fresh, stream};
+    HGX_TRY(fresh.alloc(32 * nc));
+    HGX_TRY(pub.alloc(65 * nc));
+    std::vector<uint8_t> want(65 * nc), got(65 * nc);
+    HGX_TRY(hipMemcpyAsync(fresh.p, priv32, 32 * nc, hipMemcpyHostToDevice, stream));
+    // d G beside the participant's key (a participant without a signing key keeps its own row)
+    HGX_TRY(hipMemcpyAsync(pub.p, pk_keys.p, 65 * nc, hipMemcpyDeviceToDevice, stream));
+    launch_p256_pub(stream, C, fresh.p, pk_tab.p + nc * kP256TabWords, pub.p);
+    HGX_TRY(hipGetLastError());
+    HGX_TRY(hipMemcpyAsync(got.data(), pub.p, 65 * nc, hipMemcpyDeviceToHost, stream));
+    HGX_TRY(hipMemcpyAsync(want.data(), pk_keys.p, 65 * nc, hipMemcpyDeviceToHost, stream));
+    HGX_TRY(hipStreamSynchronize(stream));
+    for (size_t c = 0; c < nc; c++)
+        if (std::memcmp(&got[65 * c], &want[65 * c], 65) != 0) {
+            *mismatch = (int32_t)c;
+            return hipSuccess;
+        }
+    HGX_TRY(wipe_signing_keys());
+    sk_keys.p = fresh.p;
+    sk_keys.n = fresh.n;
+    fresh.p = nullptr;
+    fresh.n = 0;
+    sign_has.assign(nc, 0);
+    for (size_t c = 0; c < nc; c++)
+        for (int j = 0; j < 32; j++) sign_has[c] |= priv32[32 * c + j] != 0;
+    sign_keys_set = true;
     return hipSuccess;
 }
 

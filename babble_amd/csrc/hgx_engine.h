@@ -164,6 +164,18 @@ class Engine {
     hipError_t insert_wire_bodies(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count,
                                   const WireWindows& w, uint8_t* out_id32, int64_t* out_sp, int64_t* out_op,
                                   InsertOut& out);
+    // Event.Sign on the device. set_signing_keys: C private keys of 32 big-endian bytes
+    // (each 0 = none, or in [1, N-1]: the caller checked), null clears; d G of every key is compared with
+    // the participant's key: *mismatch = the first participant whose key differs (nothing is changed
+    // then), else -1. The device copy is zeroed before it is freed. sign_insert_bodies = insert_bodies
+    // with R and S computed by the device (ev.r / ev.s are not read); out_r32 / out_s32 / out_id32 (host,
+    // may be null) get the accepted prefix.
+    hipError_t set_signing_keys(const uint8_t* priv32, int32_t* mismatch);
+    hipError_t sign_insert_bodies(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count,
+                                  const uint8_t* op_id32, uint8_t* out_r32, uint8_t* out_s32, uint8_t* out_id32,
+                                  InsertOut& out);
+    bool sign_keys_set = false;
+    std::vector<uint8_t> sign_has;   // [C] the participant has a signing key
     EvScratch* ev_scratch = nullptr;
     // The resident body store (hgx_keep_bodies, hgx_bodystore.hip): R and the
     // transaction bytes of every event, appended by insert_bodies_run behind each chunk's insert and
@@ -436,8 +448,14 @@ class Engine {
         int64_t slots;
         int64_t *out_sp, *out_op;
     };
+    struct SignOut {   // the signing path: where the accepted prefix's R and S go (host, may be null)
+        uint8_t *out_r, *out_s;
+    };
     hipError_t insert_bodies_run(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count,
-                                 const uint8_t* op_id32, uint8_t* out_id32, InsertOut& out, const WireRun* wire);
+                                 const uint8_t* op_id32, uint8_t* out_id32, InsertOut& out, const WireRun* wire,
+                                 const SignOut* sign = nullptr);
+    hipError_t wipe_signing_keys();
+    DBuf<uint8_t> sk_keys;   // [C][32] the private keys (HBM only: never saved, exported or stored with bodies)
     hipStream_t stream2 = nullptr;   // payload copies of insert_split (created on first use)
     // the pipelined ingest: stream_p and stream_o take the pieces' k_la_wave launches in turn
     int rebuild_segments(int64_t En, int coord_compact) const;

@@ -26,6 +26,8 @@
 #include "hgx_bodies.h"
 #include "hgx_bodystore.h"
 #include "hgx_engine.h"
+#include "hgx_kernels.h"
+#include "hgx_p256_sign_dev.h"
 #include "hgx_sha256_dev.h"
 
 #define HGX_TRY(x)                              \
@@ -157,13 +159,11 @@ __host__ __device__ __forceinline__ void put_i64(S& s, int64_t v) {
     put_u64(s, v < 0 ? 0 - (uint64_t)v : (uint64_t)v);
 }
 
-// big.Int.String of a 256-bit big-endian magnitude: eight 32-bit limbs divided by 10^9 nine times
+// big.Int.String of a 256-bit magnitude: eight 32-bit limbs (most significant first) divided by 10^9
+// nine times
 template <typename S>
-__host__ __device__ __forceinline__ void put_dec256(S& s, const uint8_t* be) {
-    uint32_t limb[8], chunk[9];
-#pragma unroll
-    for (int j = 0; j < 8; j++)
-        limb[j] = ((uint32_t)be[4 * j] << 24) | ((uint32_t)be[4 * j + 1] << 16) | ((uint32_t)be[4 * j + 2] << 8) | be[4 * j + 3];
+__host__ __device__ __forceinline__ void put_dec256_limbs(S& s, uint32_t limb[8]) {
+    uint32_t chunk[9];
 #pragma unroll
     for (int c = 0; c < 9; c++) {
         uint64_t rem = 0;
@@ -179,6 +179,16 @@ __host__ __device__ __forceinline__ void put_dec256(S& s, const uint8_t* be) {
 #pragma unroll
     for (int c = 8; c >= 0; c--) put_chunk9(s, chunk[c], started);
     if (!started) s.put('0');
+}
+
+// the same of 32 big-endian bytes
+template <typename S>
+__host__ __device__ __forceinline__ void put_dec256(S& s, const uint8_t* be) {
+    uint32_t limb[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+        limb[j] = ((uint32_t)be[4 * j] << 24) | ((uint32_t)be[4 * j + 1] << 16) | ((uint32_t)be[4 * j + 2] << 8) | be[4 * j + 3];
+    put_dec256_limbs(s, limb);
 }
 
 template <typename S>
@@ -230,7 +240,11 @@ struct EvCols {
     const uint8_t* keys65;   // [n_keys][65]
     const uint8_t *sp_id, *op_id;   // [m][32] the parents' ids, or null: the slots stay open
     const uint8_t* root_has_x;      // [n_keys] the creator's Root.X has an id (§3.12), or null: no root ids
+    int32_t open_sig;               // the signing path (§3.16): r / s are not read, the tail behind the body stays open
 };
+
+// The tail of an event's text behind its body, at its longest: ,"R": and ,"S": with 78 digits each, }\n
+constexpr int kSigTailMax = 5 + 78 + 5 + 78 + 2;
 
 // The roots' ids (Engine::set_root_ids, §3.12): the text of parents that are in no id column. All null
 // on a context without root ids.
@@ -281,11 +295,15 @@ __host__ __device__ __forceinline__ void encode_event(S& s, const EvCols& c, int
     put_i64(s, c.index[k]);
     s.put('}');
     body_end = s.n;
-    put_str(s, ",\"R\":");
-    put_dec256(s, c.r + 32 * k);
-    put_str(s, ",\"S\":");
-    put_dec256(s, c.s + 32 * k);
-    put_str(s, "}\n");
+    if (c.open_sig) {   // sized for the longest R and S; k_ev_sign_ids writes the tail and the true length
+        s.skip(kSigTailMax);
+    } else {
+        put_str(s, ",\"R\":");
+        put_dec256(s, c.r + 32 * k);
+        put_str(s, ",\"S\":");
+        put_dec256(s, c.s + 32 * k);
+        put_str(s, "}\n");
+    }
     s.finish();
 }
 
@@ -336,6 +354,32 @@ __global__ void __launch_bounds__(256) k_ev_write(int64_t m, EvCols c, const int
     if (body_len) body_len[k] = body_end - 8;
 }
 
+// Event k's parents' hex ids into the open slots of its text, which start at text + at (s0 / o0 = its
+// parent columns; every parent source: see k_ev_ids)
+__device__ __forceinline__ void patch_parents(int64_t k, int64_t s0, int64_t o0, int64_t at, int64_t base,
+                                              const uint8_t* store_id, uint8_t* text, const uint8_t* ids,
+                                              const int32_t* __restrict__ creator, const RootIds& rt,
+                                              const uint8_t* op_rid) {
+    const uint8_t* src = nullptr;
+    if (s0 >= 0) src = s0 < base ? store_id + 32 * s0 : ids + 32 * (s0 - base);
+    else if (rt.has_x && rt.has_x[creator[k]]) src = rt.x_id + 32 * (int64_t)creator[k];
+    if (src) {
+        ByteSink w(text + at);
+        put_hex_id<true>(w, src);
+        w.finish();
+        at += 66;
+    }
+    src = nullptr;
+    if (o0 >= 0) src = o0 < base ? store_id + 32 * o0 : ids + 32 * (o0 - base);
+    else if (o0 == kRootY && rt.y_id) src = rt.y_id + 32 * (int64_t)creator[k];
+    else if (o0 == kRootOther) src = op_rid ? op_rid + 32 * k : nullptr;
+    if (src) {
+        ByteSink w(text + at + 3);
+        put_hex_id<true>(w, src);
+        w.finish();
+    }
+}
+
 // The id pass. Workgroup j owns one graph's events of the chunk, grouped by dependency level
 // (LevelPlan); level after level its lanes stride over the level's events: patch the parents' hex ids
 // into the open slots (a parent below `base` from the store's id column, a later one from this
@@ -355,27 +399,73 @@ k_ev_ids(const int32_t* __restrict__ wg_lo, const int32_t* __restrict__ wg_nl, c
         const int32_t a = loff[lo + l], b = loff[lo + l + 1];
         for (int32_t i = a + (int32_t)threadIdx.x; i < b; i += (int32_t)blockDim.x) {
             const int64_t k = pos[i];
-            const int64_t o = off[k], s0 = sp[k], o0 = op[k];
-            int64_t at = o + slot[k];
-            const uint8_t* src = nullptr;
-            if (s0 >= 0) src = s0 < base ? store_id + 32 * s0 : ids + 32 * (s0 - base);
-            else if (rt.has_x && rt.has_x[creator[k]]) src = rt.x_id + 32 * (int64_t)creator[k];
-            if (src) {
-                ByteSink w(text + at);
-                put_hex_id<true>(w, src);
-                w.finish();
-                at += 66;
-            }
-            src = nullptr;
-            if (o0 >= 0) src = o0 < base ? store_id + 32 * o0 : ids + 32 * (o0 - base);
-            else if (o0 == kRootY && rt.y_id) src = rt.y_id + 32 * (int64_t)creator[k];
-            else if (o0 == kRootOther) src = op_rid ? op_rid + 32 * k : nullptr;
-            if (src) {
-                ByteSink w(text + at + 3);
-                put_hex_id<true>(w, src);
-                w.finish();
-            }
+            const int64_t o = off[k];
+            patch_parents(k, sp[k], op[k], o + slot[k], base, store_id, text, ids, creator, rt, op_rid);
             sha256_message<false>(text, o, len[k], 0, (uint32_t*)(ids + 32 * k));
+        }
+        __threadfence();
+        __syncthreads();
+        __threadfence();
+    }
+}
+
+// What the signing id pass reads of a staged chunk (k_ev_ids' parameters)
+struct IdPass {
+    const int32_t *wg_lo, *wg_nl, *loff, *pos;
+    const int64_t *sp, *op, *off, *slot;
+    int64_t base;
+    const uint8_t* store_id;
+    uint8_t *text, *ids;
+    const int32_t* creator;
+    RootIds rt;
+    const uint8_t* op_rid;
+};
+
+// The signing twin of k_ev_ids (hgx_sign_insert_event_bodies): the same level plan and
+// the same fence / barrier / fence between levels; an event of a level gets its parents' ids patched in,
+// its body digest (EventBody.Hash: the body plus '\n'), R and S from p256_sign_one under its creator's
+// private key (priv32 [C][32]; tg = the base point's comb table), both into the chunk's own R / S columns
+// and, with the digest, to where the verified insert reads them; then the tail ,"R":<dec>,"S":<dec>}\n
+// behind the body (the write pass left kSigTailMax bytes open), the text's true length into len[k], and
+// the id = SHA-256 of the text. kSignBlock lanes per workgroup at one wave per SIMD: no scratch.
+__global__ void __launch_bounds__(kSignBlock)
+k_ev_sign_ids(IdPass p, int64_t* __restrict__ len, const int64_t* __restrict__ body_len,
+              const uint8_t* __restrict__ priv32, const uint32_t* __restrict__ tg, uint8_t* __restrict__ col_r,
+              uint8_t* __restrict__ col_s, uint8_t* __restrict__ dig) {
+    const int32_t lo = p.wg_lo[blockIdx.x], nl = p.wg_nl[blockIdx.x];
+    for (int32_t l = 0; l < nl; l++) {
+        const int32_t a = p.loff[lo + l], b = p.loff[lo + l + 1];
+        for (int32_t i = a + (int32_t)threadIdx.x; i < b; i += (int32_t)blockDim.x) {
+            const int64_t k = p.pos[i];
+            const int64_t o = p.off[k], bl = body_len[k];
+            patch_parents(k, p.sp[k], p.op[k], o + p.slot[k], p.base, p.store_id, p.text, p.ids, p.creator, p.rt, p.op_rid);
+            uint32_t dg[8];   // the digest's bytes in memory order
+            sha256_message<true>(p.text, o + 8, bl, '\n', dg);
+            p256::Fe d, e, r, s;
+            p256::load_be_words(d, priv32 + 32 * (int64_t)p.creator[k]);
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                e[7 - j] = __builtin_bswap32(dg[j]);
+                ((uint32_t*)(dig + 32 * k))[j] = dg[j];
+            }
+            p256::p256_sign_one(r, s, d, e, tg);
+            p256::store_be(col_r + 32 * k, r);
+            p256::store_be(col_s + 32 * k, s);
+            ByteSink w(p.text + o + 8 + bl);
+            uint32_t limb[8];
+            put_str(w, ",\"R\":");
+#pragma unroll
+            for (int j = 0; j < 8; j++) limb[j] = r[7 - j];
+            put_dec256_limbs(w, limb);
+            put_str(w, ",\"S\":");
+#pragma unroll
+            for (int j = 0; j < 8; j++) limb[j] = s[7 - j];
+            put_dec256_limbs(w, limb);
+            put_str(w, "}\n");
+            w.finish();
+            const int64_t tl = 8 + bl + w.n;
+            len[k] = tl;
+            sha256_message<false>(p.text, o, tl, 0, (uint32_t*)(p.ids + 32 * k));
         }
         __threadfence();
         __syncthreads();
@@ -496,8 +586,9 @@ struct EvScratch {
             plan_levels(ev.creator + lo, level.data(), (int64_t)m, n_per_graph, plan);
         }
         const size_t nwg = with_plan ? plan.wg_lo.size() : 0, nloff = with_plan ? plan.loff.size() : 0;
-        const void* src[16] = {ev.creator + lo, ev.index + lo, ev.sp + lo, ev.op + lo, ev.ts + lo, ev.r + 32 * lo,
-                               ev.s + 32 * lo, ev.ntx + lo, nullptr, nullptr, nbytes ? ev.tx_bytes + b0 : nullptr,
+        const void* src[16] = {ev.creator + lo, ev.index + lo, ev.sp + lo, ev.op + lo, ev.ts + lo,
+                               ev.r ? ev.r + 32 * lo : nullptr,   // (null on the signing path: the device writes both)
+                               ev.s ? ev.s + 32 * lo : nullptr, ev.ntx + lo, nullptr, nullptr, nbytes ? ev.tx_bytes + b0 : nullptr,
                                keys_host, sp_id ? sp_id + 32 * lo : nullptr, op_id ? op_id + 32 * lo : nullptr, nullptr,
                                nullptr};
         size_t bytes[19] = {4 * m, 8 * m, 8 * m, 8 * m, 8 * m, 32 * m, 32 * m, 4 * m, 8 * m, 8 * (nt + 1), nbytes,
@@ -585,6 +676,16 @@ hipError_t Engine::insert_bodies(const BodiesIn& ev, const std::vector<int64_t>&
     return insert_bodies_run(ev, txi, count, op_id32, out_id32, out, nullptr);
 }
 
+// Core.SignAndInsertSelfEvent for a batch (hgx_sign_insert_event_bodies): the same chunks
+// with the texts' tails open, k_ev_sign_ids in place of k_ev_ids and k_ev_digest, and the verified insert
+// reading the R / S columns and the digests the device wrote. ev.r / ev.s are not read.
+hipError_t Engine::sign_insert_bodies(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count,
+                                      const uint8_t* op_id32, uint8_t* out_r32, uint8_t* out_s32, uint8_t* out_id32,
+                                      InsertOut& out) {
+    const SignOut so{out_r32, out_s32};
+    return insert_bodies_run(ev, txi, count, op_id32, out_id32, out, nullptr, &so);
+}
+
 // The wire route (hgx_insert_wire_bodies): the window of the resident parents is filled once, against
 // the events resident before the call; a later chunk's parents in an earlier chunk are final gids.
 hipError_t Engine::insert_wire_bodies(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count,
@@ -618,7 +719,9 @@ hipError_t Engine::insert_wire_bodies(const BodiesIn& ev, const std::vector<int6
 }
 
 hipError_t Engine::insert_bodies_run(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count,
-                                     const uint8_t* op_id32, uint8_t* out_id32, InsertOut& out, const WireRun* wire) {
+                                     const uint8_t* op_id32, uint8_t* out_id32, InsertOut& out, const WireRun* wire,
+                                     const SignOut* sign) {
+    if (sign && !sign_keys_set) return hipErrorNotReady;
     if (!ev_scratch) ev_scratch = new EvScratch();
     EvScratch& sc = *ev_scratch;
     int64_t done = 0;
@@ -647,21 +750,33 @@ hipError_t Engine::insert_bodies_run(const BodiesIn& ev, const std::vector<int64
             break;
         }
         HGX_TRY(sc.stage(ev, txi, done, hi, pk_keys.p, nullptr, C, nullptr, nullptr, true, E, n, stream, rt.has_x, op_id32));
+        sc.cols.open_sig = sign ? 1 : 0;
         if (wire && wire->win)   // window descriptors -> gids, before the encoder reads the parent columns
             launch_wire_resolve(stream, m, const_cast<int64_t*>(sc.cols.sp), const_cast<int64_t*>(sc.cols.op), wire->win,
                                 wire->slots, ins_fail.p);
         HGX_TRY(sc.size_and_scan(m, 16, stream));
         HGX_TRY(sc.write(m, (size_t)bound, true, stream));
-        const int bs = std::min(1024, std::max(64, (sc.plan.max_width + 63) & ~63));
-        hipLaunchKernelGGL(k_ev_ids, dim3((unsigned)sc.plan.wg_lo.size()), dim3(bs), 0, stream, sc.d_wg_lo, sc.d_wg_nl,
-                           sc.d_loff, sc.d_pos, sc.cols.sp, sc.cols.op, (const int64_t*)sc.d_off, (const int64_t*)sc.d_len,
-                           (const int64_t*)sc.d_slot, E, (const uint8_t*)g_id.p, sc.text.p, sc.d_ids, sc.cols.creator, rt,
-                           sc.d_op_rid);
+        const IdPass idp{sc.d_wg_lo, sc.d_wg_nl, sc.d_loff, sc.d_pos, sc.cols.sp, sc.cols.op, sc.d_off, sc.d_slot, E,
+                         g_id.p, sc.text.p, sc.d_ids, sc.cols.creator, rt, sc.d_op_rid};
+        if (sign) {
+            // a level's lanes stride over its events: the signer's workgroup is one wave whatever the width
+            hipLaunchKernelGGL(k_ev_sign_ids, dim3((unsigned)sc.plan.wg_lo.size()), dim3(kSignBlock), 0, stream, idp, sc.d_len,
+                               (const int64_t*)sc.d_blen, (const uint8_t*)sk_keys.p,
+                               (const uint32_t*)(pk_tab.p + (size_t)C * kP256TabWords), const_cast<uint8_t*>(sc.cols.r),
+                               const_cast<uint8_t*>(sc.cols.s), sc.d_dig);
+        } else {
+            const int bs = std::min(1024, std::max(64, (sc.plan.max_width + 63) & ~63));
+            hipLaunchKernelGGL(k_ev_ids, dim3((unsigned)sc.plan.wg_lo.size()), dim3(bs), 0, stream, sc.d_wg_lo, sc.d_wg_nl,
+                               sc.d_loff, sc.d_pos, sc.cols.sp, sc.cols.op, (const int64_t*)sc.d_off,
+                               (const int64_t*)sc.d_len, (const int64_t*)sc.d_slot, E, (const uint8_t*)g_id.p, sc.text.p,
+                               sc.d_ids, sc.cols.creator, rt, sc.d_op_rid);
+        }
         if (sc.n_root_other)
             hipLaunchKernelGGL(k_ev_others, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, m,
                                const_cast<int64_t*>(sc.cols.op), (const uint8_t*)sc.d_ids, sc.d_op_rid, rt.pairs, rt.n_pairs);
-        hipLaunchKernelGGL(k_ev_digest, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, m,
-                           (const uint8_t*)sc.text.p, (const int64_t*)sc.d_off, (const int64_t*)sc.d_blen, sc.d_dig);
+        if (!sign)   // (the signing id pass stored the digests it signed)
+            hipLaunchKernelGGL(k_ev_digest, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, m,
+                               (const uint8_t*)sc.text.p, (const int64_t*)sc.d_off, (const int64_t*)sc.d_blen, sc.d_dig);
         HGX_TRY(hipGetLastError());
         InsertIn in{};
         in.creator = sc.cols.creator; in.index = sc.cols.index; in.sp = sc.cols.sp; in.op = sc.cols.op;
@@ -682,8 +797,13 @@ hipError_t Engine::insert_bodies_run(const BodiesIn& ev, const std::vector<int64
             if (par[0] == kWireHoleParent || par[1] == kWireHoleParent) co.code = INS_WIRE_HOLE;
         }
         const bool want_par = wire && (wire->out_sp || wire->out_op);
-        if ((out_id32 || want_par) && co.accepted > 0) {
+        const bool want_sig = sign && (sign->out_r || sign->out_s);
+        if ((out_id32 || want_par || want_sig) && co.accepted > 0) {
             const size_t acc = (size_t)co.accepted;
+            if (sign && sign->out_r)
+                HGX_TRY(hipMemcpyAsync(sign->out_r + 32 * done, sc.cols.r, 32 * acc, hipMemcpyDeviceToHost, stream));
+            if (sign && sign->out_s)
+                HGX_TRY(hipMemcpyAsync(sign->out_s + 32 * done, sc.cols.s, 32 * acc, hipMemcpyDeviceToHost, stream));
             if (out_id32) HGX_TRY(hipMemcpyAsync(out_id32 + 32 * done, sc.d_ids, 32 * acc, hipMemcpyDeviceToHost, stream));
             if (wire && wire->out_sp)
                 HGX_TRY(hipMemcpyAsync(wire->out_sp + done, sc.cols.sp, 8 * acc, hipMemcpyDeviceToHost, stream));

@@ -343,6 +343,16 @@ size_t p256_table_bytes(int nk);
 void launch_p256_tables(hipStream_t s, int nk, const uint8_t* keys65, uint32_t* tab, uint8_t* valid);
 void launch_p256_verify(hipStream_t s, int64_t count, int nk, const int32_t* key_idx, const uint8_t* dig,
                         const uint8_t* r, const uint8_t* sg, const uint32_t* tab, const uint8_t* valid, uint8_t* out);
+// ECDSA P-256 signing (hgx_p256_sign.hip): one lane per (key index, digest) with RFC 6979
+// nonces, and d G per private key (an all-zero row of priv32 leaves its output row alone). tab_g = the
+// base point's comb table (slot nk of launch_p256_tables). kSignBlock: lanes per workgroup of every
+// signing kernel (one wave per SIMD: the signer needs the whole register file, see §3.16).
+constexpr int kSignBlock = 64;
+constexpr size_t kP256TabWords = (size_t)32 * 256 * 16;   // one key's comb table, in 32-bit words
+void launch_p256_sign(hipStream_t s, int64_t count, const int32_t* key_idx, const uint8_t* priv32, const uint8_t* dig,
+                      const uint32_t* tab_g, uint8_t* out_r, uint8_t* out_s);
+void launch_p256_pub(hipStream_t s, int nk, const uint8_t* priv32, const uint32_t* tab_g, uint8_t* out65);
+bool p256_scalar_ok(const uint8_t* d32);   // 1 <= d < N (32 bytes, big-endian)
 
 // insert path (hgx_insert.hip): events k in [0, m) get gid E0 + k
 void launch_insert_claim(hipStream_t s, int64_t m, int64_t E0, int64_t cap, int C, const InsertIn& in,

@@ -107,7 +107,12 @@ def _events32_of(cols: dict, lo: int, hi: int):
 def body_columns(creator, index, sp, op, ts, r, s, txs) -> dict:
     """hgx_event_bodies columns (include/hgx.h) of a batch: the DAG fields, the signatures' R and S
     (32 bytes big-endian each) and txs[k] = Body.Transactions of event k (None for nil, else a list of
-    byte strings)."""
+    byte strings). r = s = None: events still to be signed (Hashgraph.sign_insert_event_bodies), both
+    columns zero."""
+    if r is None:
+        r = np.zeros((len(txs), 32), np.uint8)
+    if s is None:
+        s = np.zeros((len(txs), 32), np.uint8)
     ntx = np.fromiter((-1 if t is None else len(t) for t in txs), np.int32, count=len(txs))
     flat = [b for t in txs if t for b in t]
     tx_off = np.zeros(len(flat) + 1, np.int64)
@@ -329,6 +334,37 @@ class Hashgraph:
             e.ids = ids[:e.inserted]
             raise
         return ids
+
+    def set_signing_keys(self, priv32):
+        """The private keys Event.Sign uses here (hgx_set_signing_keys): C x 32 bytes (big-endian d),
+        participant id order, 32 zero bytes = no key for that participant; None clears. Needs
+        set_participant_keys first; every key must match its participant's public key."""
+        k = None if priv32 is None else np.ascontiguousarray(priv32, np.uint8).reshape(-1, 32)
+        if k is not None and k.shape[0] != self.G * self.n:
+            raise ValueError("one private key per participant")
+        self._call(lambda ctx, e: self.L.hgx_set_signing_keys(ctx, None if k is None else ptr(k), e))
+
+    def sign_insert_event_bodies(self, cols: dict, other_parent_id32=None):
+        """Core.SignAndInsertSelfEvent for a batch (hgx_sign_insert_event_bodies): the events of
+        body_columns(..., r=None, s=None, ...) are signed on the device under their creators' signing
+        keys, hashed, verified and inserted. Returns (r, s, ids, n_inserted). Raises like insert_bodies:
+        HgxError with .inserted and the prefix's .r / .s / .ids."""
+        m = len(cols["creator"])
+        a = dict(cols, r=np.zeros((m, 32), np.uint8), s=np.zeros((m, 32), np.uint8))
+        keep, ev = _event_bodies_of(a, 0, m)
+        ev.sig_r = ev.sig_s = None   # (ignored by the call)
+        r, s, ids = (np.zeros((m, 32), np.uint8) for _ in range(3))
+        opi = None
+        if other_parent_id32 is not None:
+            opi = np.ascontiguousarray(np.asarray(other_parent_id32, np.uint8).reshape(-1, 32))
+            assert opi.shape[0] == m
+        try:
+            k = self._insert_call(self.L.hgx_sign_insert_event_bodies, C.byref(ev), None if opi is None else ptr(opi), m,
+                                  ptr(r), ptr(s), ptr(ids))
+        except HgxError as e:
+            e.r, e.s, e.ids = r[:e.inserted], s[:e.inserted], ids[:e.inserted]
+            raise
+        return r, s, ids, k
 
     def insert_verified_device(self, dt: "DeviceTrace", d_digest, d_r, lo: int = 0, hi: Optional[int] = None) -> int:
         """The same with every column resident in HBM (d_digest / d_r: device addresses of 32-byte rows)."""
@@ -1268,6 +1304,31 @@ def p256_verify(keys65, key_idx, digest, r, s, device: int = 0) -> np.ndarray:
     err = hgx_error()
     rc = _lib.lib().hgx_p256_verify_batch(device, ptr(k), k.shape[0], *[ptr(c) for c in cols], m, ptr(out),
                                           C.byref(err))
+    _lib.check(rc, err)
+    return out
+
+
+def p256_sign(priv32, key_idx, digest, device: int = 0):
+    """crypto.Sign for a batch (hgx_p256_sign_batch): digest[i] under the private key priv32[key_idx[i]]
+    (32 bytes big-endian each), RFC 6979 nonces. Returns (r [m, 32], s [m, 32])."""
+    d = np.ascontiguousarray(priv32, np.uint8).reshape(-1, 32)
+    idx = np.ascontiguousarray(key_idx, np.int32)
+    dig = np.ascontiguousarray(digest, np.uint8).reshape(-1, 32)
+    m = idx.shape[0]
+    assert dig.shape[0] == m
+    r, s = np.zeros((m, 32), np.uint8), np.zeros((m, 32), np.uint8)
+    err = hgx_error()
+    rc = _lib.lib().hgx_p256_sign_batch(device, ptr(d), d.shape[0], ptr(idx), ptr(dig), m, ptr(r), ptr(s), C.byref(err))
+    _lib.check(rc, err)
+    return r, s
+
+
+def p256_public_keys(priv32, device: int = 0) -> np.ndarray:
+    """0x04 | X | Y of d G for every private key (hgx_p256_public_keys): [n, 65]."""
+    d = np.ascontiguousarray(priv32, np.uint8).reshape(-1, 32)
+    out = np.zeros((d.shape[0], 65), np.uint8)
+    err = hgx_error()
+    rc = _lib.lib().hgx_p256_public_keys(device, ptr(d), d.shape[0], ptr(out), C.byref(err))
     _lib.check(rc, err)
     return out
 

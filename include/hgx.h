@@ -40,7 +40,9 @@ extern "C" {
                                  with hgx_prune_to_frame, hgx_get_root_ids and hgx_get_root_others, with hgx_diff_wire, and
                                  with hgx_insert_wire_bodies, and with hgx_keep_bodies and its consumers
                                  (hgx_get_event_bodies, hgx_block_transactions, hgx_get_block_hash,
-                                 hgx_block_hash_batch, hgx_diff_wire_bodies):
+                                 hgx_block_hash_batch, hgx_diff_wire_bodies), and with the signer
+                                 (hgx_p256_sign_batch, hgx_p256_public_keys, hgx_set_signing_keys,
+                                 hgx_sign_insert_event_bodies):
                                  purely additive, no existing entry or structure changed)
                               6: hgx_host_alloc / hgx_host_free (page-locked caller buffers);
                               5: hgx_events_packed (hgx_insert_events_packed, hgx_insert_and_run_packed,
@@ -274,6 +276,30 @@ int32_t hgx_insert_event_bodies(hgx_ctx* ctx, const hgx_event_bodies* ev, int64_
  * byte for byte. */
 int32_t hgx_insert_event_bodies_ext(hgx_ctx* ctx, const hgx_event_bodies* ev, const uint8_t* other_parent_id32,
                                     int64_t count, uint8_t* out_id32, int64_t* n_inserted, hgx_error* err);
+/* Event.Sign on the device. hgx_set_signing_keys: C = graphs * n_participants
+ * private keys of 32 bytes (big-endian d), participant id order; 32 zero bytes = this participant does
+ * not sign here (a real node holds one key); NULL clears. Needs hgx_set_participant_keys first (a later
+ * hgx_set_participant_keys clears the signing keys). HGX_ERR_INVALID for a d >= N, and for a key whose
+ * d G is not the participant's public key ("hgx_set_signing_keys: key <c> does not match participant
+ * <c>'s public key"); nothing is changed then. The keys live in device memory only: they are zeroed
+ * there when cleared, replaced or the context is destroyed, and never enter hgx_save / hgx_save_ex,
+ * hgx_shard_export or the body store. Signing is NOT constant time (table lookups indexed by nonce
+ * bytes): for a node that owns its GPU, or test nets.
+ *
+ * hgx_sign_insert_event_bodies: Core.SignAndInsertSelfEvent (node/core.go:122-130, 232-255) for a batch
+ * = hgx_insert_event_bodies_ext whose R and S the device computes: per event, in dependency order, the
+ * body digest, an ECDSA P-256 signature under the creator's signing key with the RFC 6979 nonce
+ * (HMAC-SHA-256; deterministic, where Go's is random: any verifier accepts either), the text with that R
+ * and S, and the id. ev->sig_r / ev->sig_s are ignored and may be NULL. out_r32 / out_s32 / out_id32
+ * (32 bytes per event, each may be NULL) receive the accepted prefix. The fresh signatures go through
+ * the same device Event.Verify as anyone's. Results, error strings, first-failure order, *n_inserted and
+ * the context's state are those of hgx_insert_event_bodies_ext on the same events carrying the same R
+ * and S. Additional refusals (HGX_ERR_INVALID "hgx_sign_insert_event_bodies: <reason>", checked on the
+ * host before anything is staged): signing keys not set; an event whose creator has no signing key. */
+int32_t hgx_set_signing_keys(hgx_ctx* ctx, const uint8_t* priv32, hgx_error* err);
+int32_t hgx_sign_insert_event_bodies(hgx_ctx* ctx, const hgx_event_bodies* ev, const uint8_t* other_parent_id32,
+                                     int64_t count, uint8_t* out_r32, uint8_t* out_s32, uint8_t* out_id32,
+                                     int64_t* n_inserted, hgx_error* err);
 /* The encoder alone: Event.Marshal bytes (json.Encoder output of {Body, R, S}, event.go:155-162) of
  * a batch whose parents' ids the caller supplies (sp_id32 / op_id32: 32 bytes per event, ignored
  * where the parent gid is -1; a parent is printed when its gid is not -1). keys65: n_keys keys of 65
@@ -782,6 +808,16 @@ int32_t hgx_p256_verify_batch(int32_t device, const uint8_t* keys65, int32_t n_k
 int32_t hgx_p256_verify_bench(int32_t device, const uint8_t* keys65, int32_t n_keys, const int32_t* key_idx,
                               const uint8_t* digest32, const uint8_t* r32, const uint8_t* s32, int64_t count,
                               int32_t warmup, int32_t iters, uint8_t* out, double* ms_per_launch);
+/* crypto.Sign (crypto/utils.go:37-39) for a batch, stand-alone like hgx_p256_verify_batch (host
+ * pointers; the base point's table is built per call): priv32 = n_keys private keys of 32 bytes
+ * (big-endian d, 1 <= d < N), key_idx[i] the key of digest i, out_r32 / out_s32 = R and S, 32 bytes
+ * big-endian each. Nonces by RFC 6979 (HMAC-SHA-256), so the output is a function of (d, digest); s
+ * is not normalised to the low half (Go's is not). hgx_p256_public_keys: 0x04 | X | Y of d G per key.
+ * HGX_ERR_INVALID for NULL pointers, n_keys <= 0, a negative count, a key index outside [0, n_keys)
+ * and a d that is 0 or not below N. Not constant time. */
+int32_t hgx_p256_sign_batch(int32_t device, const uint8_t* priv32, int32_t n_keys, const int32_t* key_idx,
+                            const uint8_t* digest32, int64_t count, uint8_t* out_r32, uint8_t* out_s32, hgx_error* err);
+int32_t hgx_p256_public_keys(int32_t device, const uint8_t* priv32, int32_t n_keys, uint8_t* out_keys65, hgx_error* err);
 
 /* ---- timing / instrumentation --------------------------------------------- */
 /* per-phase device times (ms) of the last calls: coords, rounds, fame, order; then
