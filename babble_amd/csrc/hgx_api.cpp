@@ -3089,7 +3089,7 @@ int32_t hgx_set_kernel_timing(hgx_ctx* c, int32_t on) {
 }
 
 int32_t hgx_set_fame_tally(hgx_ctx* c, int32_t mode) {
-    if (!c || mode < 0 || mode > 2) return HGX_ERR_INVALID;
+    if (!c || mode < 0 || mode > 3) return HGX_ERR_INVALID;
     each_shard(c, [&](hgx_ctx* x) { x->eng.fame_tally = mode; });
     return HGX_OK;
 }

@@ -1501,7 +1501,7 @@ hipError_t Engine::decide_fame_launch(int32_t r0, std::vector<int8_t>& fame_out)
     HGX_TRY(hipEventRecord(ph0, stream));
     HGX_TRY(hipGetLastError());   // (an error left by DivideRounds' launches surfaces there, not here)
     kbeg(K_FAME);
-    launch_fame(stream, a, r0, R, C, n, nw, sm, G, fame_tally);
+    launch_fame(stream, a, r0, R, C, n, nw, sm, G, fame_tally, num_cus);
     kend(K_FAME, 0);
     HGX_TRY(hipGetLastError());
     const size_t o = (size_t)r0 * C;

@@ -288,7 +288,8 @@ void round_pb_prof_dump(); // -DHGX_STEP_PROF builds only
 void round_g_prof_dump();  // -DHGX_STEP_PROF builds only
 // tally: 0 = witness-tiled popcount (default), 1 = per-round popcount kernel, 2 = witness-tiled int8 MFMA
 // rounds [r0, R) (r0 = the first undecided round)
-void launch_fame(hipStream_t s, const DevArrays& a, int r0, int R, int C, int n, int nw, int sm, int G, int tally);
+void launch_fame(hipStream_t s, const DevArrays& a, int r0, int R, int C, int n, int nw, int sm, int G, int tally,
+                 int num_cus);
 // rounds [r0, R) (r0 = 1 + the lowest round of an event not yet received)
 void launch_wla_transpose(hipStream_t s, const DevArrays& a, int r0, int R, int G, int C, int n);
 void launch_threshold(hipStream_t s, const DevArrays& a, int r0, int R, int C, int n);

@@ -1024,6 +1024,162 @@ __global__ void __launch_bounds__(256) k_fame_tile(int R, int r0, int XT, const 
 }
 
 // ---------------------------------------------------------------------------------
+// fame with the popcount tally, lane = voter (the default; same decisions as k_fame_tile<false>).
+// k_fame_tile's lane = witness x makes every vote bit an LDS OR and every decision an LDS CAS, and
+// every S word of a voter a dependent LDS read. Turned round, the votes and decisions of a wave are
+// ballots and nothing in the x loop depends on LDS but the (wave-uniform) V words:
+//   block  = (graph g, round i, slice xt): the witnesses x of round i among the chains
+//            [XS xt, XS xt + XS) (XS <= 64, fame_slice()); NW = ceil(n / 64) waves.
+//   lane   = voter chain y = 64 q + l of wave q, for every voting round j. A chain that is no witness
+//            of j is inactive in j (its ballot bits are 0): voters are not compacted, so bit l of
+//            word q of a vote row or a witness mask is chain 64 q + l everywhere.
+//   per j  : the lane loads its own S_j[y] (NW words), ANDs it with wm_{j-1} (each wave's ballot of
+//            the round before, NW words in LDS) and keeps it with tot = popcount, its coin bit and
+//            its witness bit in registers.
+//   per x  : V[cur][x][0..NW) are broadcast LDS reads (two x in flight), yays = sum popc(S & V[x]);
+//            the next vote word of (x, wave q) is ballot(bit) & witnesses of j, the decision of
+//            (x, wave q) is the v of the lowest lane with tt >= sm. Lane t of the wave keeps both for
+//            x = slice chain t, so a wave writes its 64 vote words and 64 decisions once per j.
+//   after the barrier of j every wave merges decw[0..NW) in ascending q into its own copy of dec
+//            (lane t = slice chain t): the lowest deciding chain wins. Every valid trace has all
+//            deciders of a round agreeing, so this is the oracle's fame whatever order
+//            it iterates in. dec is the same in every wave, so "all decided" is wave-local: one
+//            barrier per voting round. V, wm and decw alternate by parity, which keeps a wave that
+//            runs ahead into j + 1 off what a wave still in j reads.
+// j = i + 1 is See(y, x) = LA[y][cr(x)] >= Index(x): lane y walks XS consecutive entries of its
+// own WLA row (independent loads), Index(x) comes from lane x of the same wave.
+// No loop is unbounded (j <= LR) and no block waits for another.
+constexpr int kFameSlice = 64;   // chains per slice at most (one lane per x in a wave)
+
+template <int NW>
+__global__ void __launch_bounds__(64 * NW) k_fame_voter(int R, int r0, int XT, int XS, const int32_t* __restrict__ lr,
+                            const uint8_t* __restrict__ wstat, const uint8_t* __restrict__ wcoin,
+                            const int32_t* __restrict__ Bm, const int32_t* __restrict__ c_base,
+                            const int32_t* __restrict__ WLA, const uint64_t* __restrict__ Smat,
+                            int8_t* __restrict__ fame, int C, int n, int sm) {
+    __shared__ uint64_t V[2][kFameSlice][NW];      // vote bit rows V[x][w] (current / next)
+    __shared__ uint64_t wm[2][NW];                 // witness masks of rounds j-1 / j (by parity)
+    __shared__ int8_t decw[2][NW][kFameSlice];     // decision of (wave, x) in round j (by parity)
+    const int RR = R - r0;   // rounds [r0, R): the undecided ones and later
+    const int xt = blockIdx.x % XT;
+    const int i = r0 + (blockIdx.x / XT) % RR;
+    const int g = blockIdx.x / (XT * RR);
+    const int LR = lr[g];
+    if (i > LR) return;
+    const size_t gi = (size_t)g * n;
+    const int lane = lane_id();
+    const int q = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int y = 64 * q + lane;
+    const bool yin = y < n;
+    const int yc = yin ? y : 0;   // rows are read unconditionally (every chain has one) and masked after
+    const int x0 = xt * XS;
+    const int nxs = min(XS, n - x0);
+    // the slice's witnesses of round i: lane t = chain x0 + t, in every wave
+    const size_t xr = (size_t)i * C + gi + x0;
+    const bool isx = lane < nxs && wstat[xr + (lane < nxs ? lane : 0)] == 2;
+    const uint64_t xmask = __ballot(isx);
+    if (xmask == 0) return;
+    if (i + 2 > LR) {   // no round can decide: fame stays undefined
+        if (q == 0 && isx) fame[xr + lane] = 0;
+        return;
+    }
+    {   // j = i + 1
+        const size_t jr = (size_t)(i + 1) * C + gi;
+        const bool act = yin && wstat[jr + yc] == 2;
+        const uint64_t am = __ballot(act);
+        if (lane == 0) wm[(i + 1) & 1][q] = am;
+        const int32_t xi = isx ? c_base[gi + x0 + lane] + Bm[xr + lane] : 0x7FFFFFFF;   // no x: nobody sees it
+        const int32_t* __restrict__ row = WLA + (jr + yc) * n + x0;
+        uint64_t nv = 0;
+        // eight x per pass with their loads in flight together (a ballot keeps the compiler from
+        // unrolling a loop with a remainder: the tail re-reads entry nxs - 1 for lanes that are no x)
+        for (int xb = 0; xb < nxs; xb += 8) {
+            int32_t la[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) la[u] = row[min(xb + u, nxs - 1)];
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                const uint64_t b = __ballot(la[u] >= __builtin_amdgcn_readlane(xi, xb + u)) & am;
+                if (lane == xb + u) nv = b;
+            }
+        }
+        V[0][lane][q] = nv;
+    }
+    __syncthreads();
+    int dec = 0;   // lane t: the decision of chain x0 + t, the same in every wave
+    int cur = 0;
+    for (int j = i + 2; j <= LR; j++) {
+        const bool normal = ((j - i) % n) != 0;
+        const size_t jr = (size_t)j * C + gi;
+        const bool act = yin && wstat[jr + yc] == 2;
+        const uint64_t am = __ballot(act);
+        if (lane == 0) wm[j & 1][q] = am;
+        const bool coin = wcoin[jr + yc] != 0;
+        const uint64_t* __restrict__ srow = Smat + (jr + yc) * NW;
+        const uint64_t* wp = wm[(j - 1) & 1];   // witnesses of round j-1 (S rows may cover jumped candidates)
+        uint64_t S[NW];
+        int tot = 0;
+#pragma unroll
+        for (int k = 0; k < NW; k++) S[k] = srow[k];   // every lane loads (one batch), an inactive one drops it
+#pragma unroll
+        for (int k = 0; k < NW; k++) {
+            S[k] = act ? S[k] & wp[k] : 0ull;
+            tot += __popcll(S[k]);
+        }
+        uint64_t nv = 0;   // lane t: the next vote word of (chain x0 + t, this wave)
+        int nd = 0;        // lane t: this wave's decision of chain x0 + t
+        auto vote = [&](int xl, const uint64_t* vx) {
+            int yays = 0;
+#pragma unroll
+            for (int k = 0; k < NW; k++) yays += __popcll(S[k] & vx[k]);
+            const int nays = tot - yays;
+            const bool v = yays >= nays;
+            const bool strong = (v ? yays : nays) >= sm;
+            uint64_t bits;
+            if (normal) {
+                const uint64_t vb = __ballot(v);
+                const uint64_t d = __ballot(strong) & am;
+                const int val = d ? 2 - (int)((vb >> __builtin_ctzll(d)) & 1ull) : 0;
+                if (lane == xl) nd = val;
+                bits = vb & am;
+            } else {
+                bits = __ballot(strong ? v : coin) & am;
+            }
+            if (lane == xl) nv = bits;
+        };
+        // the undecided x two at a time: the V words of both are in flight before the first tally.
+        // An odd one out runs twice (the same values again).
+        for (uint64_t rem = xmask & __ballot(dec == 0); rem;) {
+            const int xa = __builtin_ctzll(rem);
+            rem &= rem - 1;
+            const int xb = rem ? __builtin_ctzll(rem) : xa;
+            rem &= rem - 1;
+            uint64_t va[NW], vb[NW];
+#pragma unroll
+            for (int k = 0; k < NW; k++) {
+                va[k] = V[cur][xa][k];
+                vb[k] = V[cur][xb][k];
+            }
+            vote(xa, va);
+            vote(xb, vb);
+        }
+        V[cur ^ 1][lane][q] = nv;
+        if (normal) decw[j & 1][q][lane] = (int8_t)nd;
+        __syncthreads();
+        if (normal) {
+#pragma unroll
+            for (int k = 0; k < NW; k++) {
+                const int d = decw[j & 1][k][lane];
+                dec = dec ? dec : d;
+            }
+        }
+        if ((xmask & __ballot(dec == 0)) == 0) break;
+        cur ^= 1;
+    }
+    if (q == 0 && isx) fame[xr + lane] = (int8_t)dec;
+}
+
+// ---------------------------------------------------------------------------------
 // WLAT[i][g][d][c] = WLA[i][g][c][d]: per round, the lastAncestors of the candidates
 // transposed so that "which witnesses of round i see chain d up to index j" is one
 // contiguous row (k_threshold, k_cts_*). 64 x 64 tiles through LDS; eligible rounds only.
@@ -2494,11 +2650,45 @@ void launch_wcoin(hipStream_t s, const DevArrays& a, int r0, int R, int C) {
                        a.g_coin, a.wcoin + o);
 }
 
-// fame kernel choice (hgx_set_fame_tally): the witness-tiled kernel with the popcount tally
-// by default (measured faster than the int8 MFMA tally at every n); the
-// per-round popcount kernel and the MFMA tally stay selectable for measurement.
-void launch_fame(hipStream_t s, const DevArrays& a, int r0, int R, int C, int n, int nw, int sm, int G, int tally) {
+// chains per slice of k_fame_voter. A lane's setup per voting round (its S row, nw words) is shared
+// by the x of the slice, so the widest slice (64, one x per lane of a wave) does the least work: at
+// nw = 4 the setup is about one x's worth of instructions, 1/64 of a full slice. A narrower slice
+// only pays where the grid would otherwise leave the device idle: a CU holds 32 waves, so 32 / nw
+// blocks (8 counted at most), and below two rounds of blocks over all CUs the slice halves, down to
+// 16 (setup 1/16 of the x loop). c3 (256 chains, 2 838 rounds): 64, 11 352 blocks of 4 waves.
+// c5 (1 024 chains, 56 rounds): 896 blocks of 16 waves at 64 against 512 slots, so 32 (1 792).
+// A resumed call's handful of rounds: 16, the shortest x loop per block.
+static int fame_slice(int n, int nw, int64_t graph_rounds, int num_cus) {
+    const int64_t slots = (int64_t)num_cus * std::max(1, std::min(8, 32 / nw));
+    int xs = kFameSlice;
+    while (xs > 16 && graph_rounds * ((n + xs - 1) / xs) < 2 * slots) xs >>= 1;
+    return xs;
+}
+
+// fame kernel choice (hgx_set_fame_tally): the popcount tally with lane = voter by default
+// (k_fame_voter); the per-round popcount kernel (1), the witness-tiled kernel
+// with the int8 MFMA tally (2) or the popcount tally (3) stay selectable for measurement and
+// as references for each other in the tests.
+void launch_fame(hipStream_t s, const DevArrays& a, int r0, int R, int C, int n, int nw, int sm, int G, int tally,
+                 int num_cus) {
     if (R <= r0) return;
+    if (tally == 0 && n <= kFameMaxW * 64) {
+        const int XS = fame_slice(n, nw, (int64_t)G * (R - r0), num_cus);
+        const int XT = (n + XS - 1) / XS;
+        const dim3 grid((unsigned)((int64_t)G * (R - r0) * XT));
+#define FV_LAUNCH(NW)                                                                                              \
+    case NW:                                                                                                       \
+        hipLaunchKernelGGL(k_fame_voter<NW>, grid, dim3(64 * NW), 0, s, R, r0, XT, XS, a.lr, a.wstat, a.wcoin, a.Bm, \
+                           a.c_base, a.WLA, a.Smat, a.fame, C, n, sm);                                             \
+        break;
+        switch (nw) {
+            FV_LAUNCH(1) FV_LAUNCH(2) FV_LAUNCH(3) FV_LAUNCH(4) FV_LAUNCH(5) FV_LAUNCH(6) FV_LAUNCH(7) FV_LAUNCH(8)
+            FV_LAUNCH(9) FV_LAUNCH(10) FV_LAUNCH(11) FV_LAUNCH(12) FV_LAUNCH(13) FV_LAUNCH(14) FV_LAUNCH(15)
+            FV_LAUNCH(16)
+        }
+#undef FV_LAUNCH
+        return;
+    }
     const int mode = tally == 1 ? 0 : tally == 2 ? 2 : 1;
     if (mode != 0 && n <= kFameMaxW * 64) {
         const int XT = (n + kFameTile - 1) / kFameTile;

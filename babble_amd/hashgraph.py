@@ -1022,8 +1022,9 @@ class Hashgraph:
             raise ValueError(f"invalid ingest pipeline {pieces}, {min_events}")
 
     def set_fame_tally(self, mode):
-        """DecideFame tally: "popc" (default), "vote" (per-round kernel) or "mfma" (int8 MFMA)."""
-        m = {"popc": 0, "vote": 1, "mfma": 2}[mode] if isinstance(mode, str) else int(mode)
+        """DecideFame tally: "popc" (default, one lane per voter), "vote" (per-round kernel), "mfma"
+        (witness-tiled, int8 MFMA) or "tile" (witness-tiled popcount)."""
+        m = {"popc": 0, "vote": 1, "mfma": 2, "tile": 3}[mode] if isinstance(mode, str) else int(mode)
         if self.L.hgx_set_fame_tally(self.ctx, m) != 0:
             raise ValueError(f"invalid fame tally {mode}")
 

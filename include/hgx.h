@@ -850,8 +850,9 @@ int32_t hgx_set_kernel_timing(hgx_ctx* ctx, int32_t mask);
 /* coordinate storage of later DivideRounds calls: 0 = auto (uint16 when every Index
  * <= 65533 and n is even, else int32), 1 = always int32. Same results either way. */
 int32_t hgx_set_coord_storage(hgx_ctx* ctx, int32_t mode);
-/* DecideFame vote tally: 0 = witness-tiled popcount (default), 1 = per-round popcount
- * kernel, 2 = witness-tiled int8 MFMA. Same results; for measurement. */
+/* DecideFame vote tally: 0 = popcount with one lane per voter (default), 1 = per-round popcount
+ * kernel, 2 = witness-tiled int8 MFMA, 3 = witness-tiled popcount (the default before the
+ * lane-per-voter kernel). Same results; for measurement. */
 int32_t hgx_set_fame_tally(hgx_ctx* ctx, int32_t mode);
 /* hgx_insert_and_run32 on an empty, unrooted, unsharded one-graph context of n <= 896 with at least
  * min_events events (default 4 000 000) and a time-segmented lastAncestors pass: the structure columns
