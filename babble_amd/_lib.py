@@ -154,6 +154,7 @@ def lib():
     _sig(L, "hgx_insert_event_bodies", i32, [p, C.POINTER(hgx_event_bodies), i64, p, C.POINTER(C.c_int64), E])
     _sig(L, "hgx_insert_event_bodies_ext", i32, [p, C.POINTER(hgx_event_bodies), p, i64, p, C.POINTER(C.c_int64), E])
     _sig(L, "hgx_set_signing_keys", i32, [p, p, E])
+    _sig(L, "hgx_insert_event_bodies_claimed", i32, [p, C.POINTER(hgx_event_bodies), p, p, i64, C.POINTER(C.c_int64), E])
     _sig(L, "hgx_sign_insert_event_bodies", i32, [p, C.POINTER(hgx_event_bodies), p, i64, p, p, p, C.POINTER(C.c_int64), E])
     _sig(L, "hgx_p256_sign_batch", i32, [i32, p, i32, p, p, i64, p, p, E])
     _sig(L, "hgx_p256_public_keys", i32, [i32, p, i32, p, E])
@@ -166,6 +167,7 @@ def lib():
     _sig(L, "hgx_get_event_payload", i32, [p, i64, p, i64, C.POINTER(C.c_int64), E])
     _sig(L, "hgx_checksum", u64, [p, i64])
     _sig(L, "hgx_bootstrap", i32, [p, C.c_char_p, E])
+    _sig(L, "hgx_save_bodies", i32, [p, C.c_char_p, E])
     _sig(L, "hgx_clear", i32, [p])
     for nm in ("hgx_divide_rounds", "hgx_decide_fame", "hgx_find_order", "hgx_run_consensus"):
         _sig(L, nm, i32, [p, E])

@@ -22,6 +22,7 @@
 #include "hgx.h"
 #include "hgx_bodies.h"
 #include "hgx_bodystore.h"
+#include "hgx_ckpt_host.h"
 #include "hgx_diff.h"
 #include "hgx_engine.h"
 #include "hgx_wire_plan.h"
@@ -506,6 +507,11 @@ static int32_t finish_insert(hgx_ctx* c, const hgx::InsertOut& out, int64_t* n_i
             rc = HGX_ERR_CAPACITY;
             msg = "hgx_keep_bodies: the body store could not grow (out of device memory)";
             break;
+        case hgx::INS_ID_MISMATCH:   // (the flat id pass: the position inside the call is the accepted count)
+            rc = HGX_ERR_INVALID;
+            msg = "hgx_insert_event_bodies_claimed: event " + std::to_string(out.accepted) +
+                  ": the claimed id is not the event's hash";
+            break;
         case hgx::INS_WIRE_HOLE:   // (a bug: the host plan named a resident event the window kernel did not find)
             rc = HGX_ERR_PANIC;
             msg = "hgx_insert_wire_bodies: a resident parent's window slot was not filled";
@@ -865,17 +871,22 @@ int32_t hgx_insert_events_verified_device(hgx_ctx* c, const hgx_events* ev, cons
 //  self-parent -1, HGX_ROOT_Y and HGX_ROOT_OTHER print the roots' ids.
 // sign (hgx_sign_insert_event_bodies): R and S come from the device (evb's are not read),
 // out_r32 / out_s32 get the accepted prefix's; everything else is the same call.
+// claimed (hgx_insert_event_bodies_claimed): claimed_id32 carries every event's id, which the
+// flat pass proves instead of hashing level after level; everything else is the same call.
 static int32_t insert_event_bodies_impl(hgx_ctx* c, const hgx_event_bodies* evb, const uint8_t* other_parent_id32,
                                         int64_t count, bool sign, uint8_t* out_r32, uint8_t* out_s32, uint8_t* out_id32,
-                                        int64_t* n_inserted, hgx_error* err) {
-    const char* fn = sign ? "hgx_sign_insert_event_bodies" : "hgx_insert_event_bodies";
+                                        int64_t* n_inserted, hgx_error* err, bool claimed = false,
+                                        const uint8_t* claimed_id32 = nullptr) {
+    const char* fn = claimed ? "hgx_insert_event_bodies_claimed"
+                     : sign  ? "hgx_sign_insert_event_bodies"
+                             : "hgx_insert_event_bodies";
     const std::string who = std::string(fn) + ": ";
     auto bad = [&](const std::string& why) {
         set_err(err, HGX_ERR_INVALID, who + why);
         return (int32_t)HGX_ERR_INVALID;
     };
     if (n_inserted) *n_inserted = 0;
-    if (!evb || count < 0) return bad("bad arguments");
+    if (!evb || count < 0 || (claimed && !claimed_id32)) return bad("bad arguments");
     const hgx::BodiesIn ev{evb->creator, evb->index, evb->self_parent, evb->other_parent, evb->timestamp_ns,
                            sign ? nullptr : evb->sig_r, sign ? nullptr : evb->sig_s, evb->ntx, evb->tx_off, evb->tx_bytes};
     std::vector<int64_t> txi;
@@ -899,8 +910,9 @@ static int32_t insert_event_bodies_impl(hgx_ctx* c, const hgx_event_bodies* evb,
     const int64_t cut = hgx::bodies_first_unencodable(ev, count, c->E, c->C, root_ids ? c->root_has_y.data() : nullptr,
                                                       other_parent_id32 != nullptr);
     hgx::InsertOut out;
-    hipError_t e = sign ? c->eng.sign_insert_bodies(ev, txi, cut, other_parent_id32, out_r32, out_s32, out_id32, out)
-                        : c->eng.insert_bodies(ev, txi, cut, other_parent_id32, out_id32, out);
+    hipError_t e = claimed ? c->eng.insert_bodies_claimed(ev, txi, cut, other_parent_id32, claimed_id32, out)
+                   : sign  ? c->eng.sign_insert_bodies(ev, txi, cut, other_parent_id32, out_r32, out_s32, out_id32, out)
+                           : c->eng.insert_bodies(ev, txi, cut, other_parent_id32, out_id32, out);
     if (e != hipSuccess) return dev_err(err, e, fn);
     if (out.code == hgx::INS_OK && cut < count) {
         // the cut event's own checks (it cannot pass them: its creator or a parent is unknown)
@@ -959,6 +971,15 @@ int32_t hgx_set_signing_keys(hgx_ctx* c, const uint8_t* priv32, hgx_error* err) 
         return bad("key " + std::to_string(mismatch) + " does not match participant " + std::to_string(mismatch) +
                    "'s public key");
     return ok(err);
+}
+
+// InsertEvent for events that come with their ids (a checkpoint, a Frame, Badger): one flat hash pass proves
+// every claimed id; the first that is not its event's hash ends the call behind the proven prefix
+int32_t hgx_insert_event_bodies_claimed(hgx_ctx* c, const hgx_event_bodies* evb, const uint8_t* claimed_id32,
+                                        const uint8_t* other_parent_id32, int64_t count, int64_t* n_inserted,
+                                        hgx_error* err) {
+    return insert_event_bodies_impl(c, evb, other_parent_id32, count, false, nullptr, nullptr, nullptr, n_inserted, err, true,
+                                    claimed_id32);
 }
 
 int32_t hgx_insert_event_bodies(hgx_ctx* c, const hgx_event_bodies* evb, int64_t count, uint8_t* out_id32,
@@ -1219,24 +1240,49 @@ struct CkptReader {
 };
 }  // namespace
 
-enum : int32_t { kCkRooted = 1, kCkIds = 2, kCkKeys = 4, kCkPayloads = 8 };
+using hgx::kCkBodies;   // (the flags: hgx_ckpt_host.h)
+using hgx::kCkIds;
+using hgx::kCkKeys;
+using hgx::kCkPayloads;
+using hgx::kCkRooted;
 
-int32_t hgx_save_ex(hgx_ctx* c, const char* path, const int64_t* payload_off, const uint8_t* payload, hgx_error* err) {
+// The store's slices of hgx_save_bodies go through the file in pieces of at most this many entries / bytes
+static constexpr int64_t kSavePiece = 4 << 20;
+
+// hgx_save / hgx_save_ex (version 2) and, with bodies, hgx_save_bodies (version 3: the roots' ids and pairs
+// and the kept blocks' hashes behind the rooted section, R and the transactions behind the keys)
+static int32_t save_impl(hgx_ctx* c, const char* path, const int64_t* payload_off, const uint8_t* payload, bool bodies,
+                         hgx_error* err) {
+    const std::string who = bodies ? "hgx_save_bodies" : "hgx_save";
     if (!c || !path || (payload_off && !payload && c->E > 0)) {
-        set_err(err, HGX_ERR_INVALID, "hgx_save: bad arguments");
+        set_err(err, HGX_ERR_INVALID, who + ": bad arguments");
         return HGX_ERR_INVALID;
+    }
+    if (bodies) {
+        const char* why = c->grp                                              ? "not available on a chain-sharded context"
+                          : c->shard_world > 1                                ? "not available on a row-sharded context"
+                          : c->eng.bodies_state != hgx::kBodiesComplete       ? "bodies not known"
+                          : !c->eng.ids_known                                 ? "ids not known"
+                          : (c->rooted && !c->root_ids_known)                 ? "root ids not known"
+                          : !c->eng.keys_set                                  ? "participant keys not set"
+                          : c->eng.bodies_events != c->E                      ? "bodies not known"
+                                                                              : nullptr;
+        if (why) {
+            set_err(err, HGX_ERR_INVALID, who + ": " + why);
+            return HGX_ERR_INVALID;
+        }
     }
     DeviceGuard dg(c);
     std::vector<int32_t> creator, index, sp, op, ntx;
     std::vector<int64_t> ts;
     std::vector<uint8_t> S, coin, nil, ids, keys;
     hipError_t e = c->eng.get_columns(creator, index, sp, op, ts, S, coin, ntx, nil);
-    if (e != hipSuccess) return dev_err(err, e, "hgx_save");
+    if (e != hipSuccess) return dev_err(err, e, who.c_str());
     const int64_t E = (int64_t)creator.size();
-    const bool have_ids = c->eng.ids_known && E > 0;
+    const bool have_ids = (c->eng.ids_known && E > 0) || bodies;   // (version 3 always carries the section)
     if (have_ids) {
         ids.resize((size_t)E * 32);
-        e = c->eng.get_ids(0, E, ids.data());
+        if (E > 0) e = c->eng.get_ids(0, E, ids.data());
         if (e != hipSuccess) return dev_err(err, e, "hgx_save");
     }
     if (c->eng.keys_set) {
@@ -1258,13 +1304,13 @@ int32_t hgx_save_ex(hgx_ctx* c, const char* path, const int64_t* payload_off, co
     const std::string tmp = std::string(path) + ".tmp";
     FILE* f = std::fopen(tmp.c_str(), "wb");
     if (!f) {
-        set_err(err, HGX_ERR_INVALID, std::string("hgx_save: cannot open ") + tmp);
+        set_err(err, HGX_ERR_INVALID, who + ": cannot open " + tmp);
         return HGX_ERR_INVALID;
     }
     CkptWriter w{f};
-    const uint32_t version = 2;
+    const uint32_t version = bodies ? 3 : 2;
     const int32_t flags = (c->rooted ? kCkRooted : 0) | (have_ids ? kCkIds : 0) | (keys.empty() ? 0 : kCkKeys) |
-                          (payload_off ? kCkPayloads : 0);
+                          (payload_off ? kCkPayloads : 0) | (bodies ? kCkBodies : 0);
     w.put(kCkptMagic, 8);
     w.put(&version, 4);
     w.put(&c->n, 4);
@@ -1296,6 +1342,27 @@ int32_t hgx_save_ex(hgx_ctx* c, const char* path, const int64_t* payload_off, co
                 w.put(a1, 8);
             }
         }
+        if (bodies) {   // the roots' ids, the Root.Others pairs (sorted by event id) and the kept blocks' hashes
+            std::vector<uint8_t> has(c->root_has_x);
+            has.insert(has.end(), c->root_has_y.begin(), c->root_has_y.end());
+            has.resize((has.size() + 3) & ~(size_t)3, 0);
+            w.put(has.data(), has.size());
+            w.put(c->root_x_id.data(), (size_t)c->C * 32);
+            w.put(c->root_y_id.data(), (size_t)c->C * 32);
+            const int64_t np = (int64_t)c->root_others.size();
+            w.put(&np, 8);
+            for (int half = 0; half < 2; half++)
+                for (const auto& pr : c->root_others) w.put(pr.data() + 32 * half, 32);
+            for (int g = 0; g < c->G; g++) {
+                if (g >= (int)c->reset_kept.size()) continue;
+                for (const Block& b : c->reset_kept[g].blocks) {
+                    uint8_t rec[36] = {};
+                    rec[0] = b.has_hash ? 1 : 0;
+                    if (b.has_hash) std::memcpy(rec + 4, b.hash, 32);
+                    w.put(rec, 36);
+                }
+            }
+        }
     }
     std::vector<int64_t> wide((size_t)E);
     w.put(creator.data(), (size_t)E * 4);
@@ -1314,19 +1381,181 @@ int32_t hgx_save_ex(hgx_ctx* c, const char* path, const int64_t* payload_off, co
         w.put(payload_off, (size_t)(E + 1) * 8);
         w.put(payload, (size_t)payload_off[E]);
     }
+    if (bodies) {
+        // R, then the transaction table and the arena in slices: the store is in gid order, so host memory
+        // beyond the per-event columns is one piece
+        std::vector<uint8_t> piece;
+        auto slices = [&](hgx::Engine::BodyTable which, int64_t lo, int64_t count, size_t width, int64_t rebase) {
+            for (int64_t at = 0; at < count && e == hipSuccess; at += kSavePiece) {
+                const int64_t m = std::min(kSavePiece, count - at);
+                piece.resize((size_t)m * width);
+                e = c->eng.bodies_read(which, lo + at, m, piece.data());
+                if (e != hipSuccess) break;
+                if (rebase) {
+                    int64_t* o = (int64_t*)piece.data();
+                    for (int64_t j = 0; j < m; j++) o[j] -= rebase;
+                }
+                w.put(piece.data(), piece.size());
+            }
+        };
+        const int64_t T = c->eng.bodies_tx;
+        int64_t ends[2] = {0, 0};   // the arena run of the resident events: [tx_off[0], tx_off[T])
+        e = c->eng.bodies_read(hgx::Engine::kBodyOffsets, 0, 1, &ends[0]);
+        if (e == hipSuccess) e = c->eng.bodies_read(hgx::Engine::kBodyOffsets, T, 1, &ends[1]);
+        slices(hgx::Engine::kBodyRows, 0, E, 32, 0);
+        w.put(&T, 8);
+        slices(hgx::Engine::kBodyOffsets, 0, T + 1, 8, ends[0]);
+        slices(hgx::Engine::kBodyArena, ends[0], ends[1] - ends[0], 1, 0);
+        if (e != hipSuccess) {
+            std::fclose(f);
+            std::remove(tmp.c_str());
+            return dev_err(err, e, who.c_str());
+        }
+    }
     const uint64_t sum = w.h;
     w.put(&sum, 8);
     const bool ok_w = w.ok && std::fflush(f) == 0;
     std::fclose(f);
     if (!ok_w || std::rename(tmp.c_str(), path) != 0) {
         std::remove(tmp.c_str());
-        set_err(err, HGX_ERR_INVALID, std::string("hgx_save: write failed: ") + path);
+        set_err(err, HGX_ERR_INVALID, who + ": write failed: " + path);
         return HGX_ERR_INVALID;
     }
     return ok(err);
 }
 
-int32_t hgx_save(hgx_ctx* c, const char* path, hgx_error* err) { return hgx_save_ex(c, path, nullptr, nullptr, err); }
+int32_t hgx_save_ex(hgx_ctx* c, const char* path, const int64_t* payload_off, const uint8_t* payload, hgx_error* err) {
+    return save_impl(c, path, payload_off, payload, false, err);
+}
+
+int32_t hgx_save(hgx_ctx* c, const char* path, hgx_error* err) { return save_impl(c, path, nullptr, nullptr, false, err); }
+
+// The checkpoint of a keeping context: version 3, with every event's R and transactions
+int32_t hgx_save_bodies(hgx_ctx* c, const char* path, hgx_error* err) { return save_impl(c, path, nullptr, nullptr, true, err); }
+
+// A version-3 file (hgx_save_bodies). Pass 1: hgx_ckpt_host.cpp checks the checksum and
+// every section with the context untouched. Pass 2 replays: roots, kept state, keys and root ids, then the
+// events in pieces through the claimed path, which proves every id in the file (the flat pass) and every
+// signature (Event.Verify), then one consensus run. A failure of the replay leaves the accepted prefix
+// resident, as a version-2 file does.
+static int32_t bootstrap_v3(hgx_ctx* c, const std::vector<uint8_t>& image, hgx_error* err) {
+    auto bad = [&](const std::string& why) {
+        set_err(err, HGX_ERR_INVALID, "hgx_bootstrap: " + why);
+        return (int32_t)HGX_ERR_INVALID;
+    };
+    hgx::Ckpt3 f;
+    std::string why;
+    if (hgx::ckpt3_parse(image.data(), image.size(), c->n, c->G, f, why)) return bad(why);
+    if (f.E > c->eng.cap)
+        return bad("the file has " + std::to_string(f.E) + " events, the context's capacity is " + std::to_string(c->eng.cap));
+    if (c->grp) return bad("not available on a chain-sharded context");
+    if (c->shard_world > 1) return bad("not available on a row-sharded context");
+    using hgx::ckpt_rd;
+    const size_t Cz = (size_t)c->C;
+    if (f.flags & kCkRooted) {
+        std::vector<int32_t> ri(Cz), rr(Cz), ry(Cz), hx(Cz), hy(Cz);
+        for (size_t p = 0; p < Cz; p++) {
+            ri[p] = ckpt_rd<int32_t>(f.root_index, (int64_t)p);
+            rr[p] = ckpt_rd<int32_t>(f.root_round, (int64_t)p);
+            ry[p] = f.root_y[p];
+            hx[p] = f.has_x[p];
+            hy[p] = f.has_y[p];
+        }
+        int32_t rc = hgx_reset(c, ri.data(), rr.data(), ry.data(), err);
+        if (rc) return rc;
+        std::vector<hgx_ctx::Kept> kept((size_t)f.G);
+        for (int g = 0; g < f.G; g++) {
+            const hgx::Ckpt3Kept& fk = f.kept[(size_t)g];
+            hgx_ctx::Kept& k = kept[(size_t)g];
+            k.has_lcr = fk.has_lcr != 0;
+            k.lcr = fk.lcr;
+            k.lcre = fk.lcre;
+            k.consensus_tx = fk.consensus_tx;
+            k.blocks.resize((size_t)fk.n_blocks);
+            for (int64_t b = 0; b < fk.n_blocks; b++) {
+                const uint8_t *rec = fk.blocks + hgx::kCkptBlockBytes * (size_t)b, *h = fk.hashes + hgx::kCkptBlockHashBytes * (size_t)b;
+                Block& blk = k.blocks[(size_t)b];
+                blk.rr = ckpt_rd<int32_t>(rec, 0);
+                blk.nev = ckpt_rd<int32_t>(rec, 1);
+                blk.ntx = ckpt_rd<int64_t>(rec + 8);
+                blk.tx_nil = ckpt_rd<int32_t>(rec + 16, 0);
+                blk.committed = ckpt_rd<int32_t>(rec + 16, 1);
+                blk.first = -1;
+                blk.has_hash = h[0];
+                std::memcpy(blk.hash, h + 4, 32);
+            }
+            GraphState& s = c->gs[g];
+            s.has_lcr = k.has_lcr;
+            s.lcr = k.lcr;
+            s.lcre = k.lcre;
+            s.consensus_tx = k.consensus_tx;
+            s.blocks = k.blocks;
+        }
+        c->reset_kept = kept;
+        rc = hgx_set_participant_keys(c, f.keys, err);
+        if (rc) return rc;
+        // (the pairs' event ids become the Root.Others keys: the parser found them equal to the keys section)
+        rc = hgx_set_root_ids(c, f.x_id, hx.data(), f.y_id, hy.data(), f.pair_event, f.pair_parent, f.n_pairs, err);
+        if (rc) return rc;
+    } else {
+        const int32_t rc = hgx_set_participant_keys(c, f.keys, err);
+        if (rc) return rc;
+    }
+    DeviceGuard dg(c);
+    // a keeping context: the store grows once to the file's totals, so no doubling runs during the replay
+    if (c->eng.bodies_state == hgx::kBodiesComplete && c->eng.bodies_events == 0 && f.E > 0 &&
+        c->eng.bodies_reserve(f.T, f.n_bytes) != hipSuccess)
+        return dev_err(err, hipErrorOutOfMemory, "hgx_bootstrap");
+    std::vector<int32_t> creator, ntx;
+    std::vector<int64_t> index, sp, op, ts, off;
+    std::vector<uint8_t> opid;
+    int64_t lo = 0, t_lo = 0;
+    while (lo < f.E) {
+        int64_t hi = lo, t_hi = t_lo;
+        hgx::ckpt3_piece(f, lo, t_lo, hgx::kBodyChunkEvents, hgx::kBodyChunkBytes / 2, &hi, &t_hi);
+        if (hi <= lo) return bad("truncated file");   // (unreachable on a validated image)
+        const size_t m = (size_t)(hi - lo), nt = (size_t)(t_hi - t_lo);
+        creator.resize(m); ntx.resize(m); index.resize(m); sp.resize(m); op.resize(m); ts.resize(m); off.resize(nt + 1);
+        std::memcpy(creator.data(), f.creator + 4 * (size_t)lo, 4 * m);
+        std::memcpy(index.data(), f.index + 8 * (size_t)lo, 8 * m);
+        std::memcpy(sp.data(), f.sp + 8 * (size_t)lo, 8 * m);
+        std::memcpy(op.data(), f.op + 8 * (size_t)lo, 8 * m);
+        std::memcpy(ts.data(), f.ts + 8 * (size_t)lo, 8 * m);
+        std::memcpy(off.data(), f.tx_off + 8 * (size_t)t_lo, 8 * (nt + 1));
+        const int64_t b0 = off[0];
+        for (int64_t& o : off) o -= b0;
+        bool any_other = false;
+        for (size_t k = 0; k < m; k++) {
+            ntx[k] = f.nil[(size_t)lo + k] ? -1 : ckpt_rd<int32_t>(f.ntx, lo + (int64_t)k);
+            any_other |= op[k] == HGX_ROOT_OTHER;
+        }
+        if (any_other) {   // the other-parent's id from the file's pairs; without a pair the device's own check fails it
+            opid.assign(32 * m, 0);
+            for (size_t k = 0; k < m; k++) {
+                if (op[k] != HGX_ROOT_OTHER) continue;
+                const int64_t j = hgx::ckpt3_find_pair(f, f.ids + 32 * ((size_t)lo + k));
+                if (j >= 0) std::memcpy(opid.data() + 32 * k, f.pair_parent + 32 * (size_t)j, 32);
+            }
+        }
+        const hgx_event_bodies evb{creator.data(), index.data(), sp.data(), op.data(), ts.data(), f.sig_r + 32 * (size_t)lo,
+                                   f.sig_s + 32 * (size_t)lo, ntx.data(), off.data(), f.tx_bytes + b0};
+        int64_t ins = 0;
+        hgx_error own;
+        if (!err) err = &own;
+        const int32_t rc = hgx_insert_event_bodies_claimed(c, &evb, f.ids + 32 * (size_t)lo, any_other ? opid.data() : nullptr,
+                                                           (int64_t)m, &ins, err);
+        if (rc) {
+            const std::string mine = "hgx_insert_event_bodies_claimed: event " + std::to_string(ins) +
+                                     ": the claimed id is not the event's hash";
+            if (rc == HGX_ERR_INVALID && mine == err->msg)
+                return bad("event " + std::to_string(lo + ins) + ": the file's id is not the event's hash");
+            return rc;
+        }
+        lo = hi;
+        t_lo = t_hi;
+    }
+    return hgx_run_consensus(c, err);
+}
 
 int32_t hgx_bootstrap(hgx_ctx* c, const char* path, hgx_error* err) {
     if (!c || !path) {
@@ -1364,6 +1593,11 @@ int32_t hgx_bootstrap(hgx_ctx* c, const char* path, hgx_error* err) {
     r.get(&flags, 4);
     r.get(&E, 8);
     if (std::memcmp(magic, kCkptMagic, 8) != 0) return bad("not a checkpoint file");
+    if (version == 3) {   // (the image with its checksum again: the version-3 parser checks the whole file)
+        r.buf.resize(r.buf.size() + 8);
+        std::memcpy(r.buf.data() + r.buf.size() - 8, &stored, 8);
+        return bootstrap_v3(c, r.buf, err);
+    }
     if (version != 1 && version != 2) return bad("unsupported version " + std::to_string(version));
     if (version == 1 && (flags & ~kCkRooted)) return bad("unsupported flags");
     if (n != c->n || G != c->G)

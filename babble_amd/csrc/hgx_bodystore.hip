@@ -242,6 +242,19 @@ hipError_t Engine::bodies_append(const uint8_t* r, const int64_t* txi, const int
     return hipSuccess;
 }
 
+hipError_t Engine::bodies_read(BodyTable which, int64_t lo, int64_t count, void* dst) {
+    if (bodies_state != kBodiesComplete || lo < 0 || count < 0 || !dst) return hipErrorInvalidValue;
+    if (count == 0) return hipSuccess;
+    const int64_t have = which == kBodyRows ? bodies_events : which == kBodySlots ? bodies_events + 1
+                         : which == kBodyOffsets ? bodies_tx + 1 : bodies_bytes;
+    if (lo + count > have) return hipErrorInvalidValue;
+    const size_t w = which == kBodyRows ? 32 : which == kBodyArena ? 1 : 8;
+    const uint8_t* src = which == kBodyRows ? b_R.p : which == kBodySlots ? (const uint8_t*)b_txi.p
+                         : which == kBodyOffsets ? (const uint8_t*)b_off.p : b_arena.p;
+    HGX_TRY(hipMemcpyAsync(dst, src + (size_t)lo * w, (size_t)count * w, hipMemcpyDeviceToHost, stream));
+    return hipStreamSynchronize(stream);
+}
+
 // The sizing half of a gather: the list (host gids, or a device list of either width) measured and
 // scanned, its totals read back. plan keeps what the copy half needs.
 hipError_t Engine::bodies_measure(const int64_t* gids_host, const int64_t* gids_dev64, const int32_t* gids_dev32,

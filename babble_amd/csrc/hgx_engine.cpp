@@ -674,12 +674,14 @@ hipError_t Engine::stage_sig(const uint8_t* digest, const uint8_t* r, int64_t co
 }
 
 hipError_t Engine::insert_verified(const InsertIn& in, const uint8_t* digest, const uint8_t* r, int64_t count,
-                                   InsertOut& out) {
+                                   InsertOut& out, bool fail_armed) {
     if (!keys_set) return hipErrorNotReady;
     if (count > 0) {
         if (pk_out.n < (size_t)count) HGX_TRY(pk_out.alloc((size_t)count));
-        if (ins_fail_sig.n < 1) HGX_TRY(ins_fail_sig.alloc(1));
-        HGX_TRY(hipMemsetAsync(ins_fail_sig.p, 0xFF, 8, stream));
+        if (!fail_armed) {
+            if (ins_fail_sig.n < 1) HGX_TRY(ins_fail_sig.alloc(1));
+            HGX_TRY(hipMemsetAsync(ins_fail_sig.p, 0xFF, 8, stream));
+        }
         // Event.Verify of the whole batch (hgx_p256.hip; key = the creator's), then its first failure
         launch_p256_verify(stream, count, C, in.creator, digest, r, in.S, pk_tab.p, pk_valid.p, pk_out.p);
         launch_insert_sig_first(stream, count, C, in.creator, pk_out.p, ins_fail_sig.p);

@@ -141,8 +141,9 @@ class Engine {
     hipError_t insert(const InsertIn& in, int64_t count, InsertOut& out);
     // the same with Event.Verify first (hashgraph.go:356-363): digest (EventBody.Hash) and R per
     // event, S = in.S, key = the creator's (set_keys); device pointers
+    // fail_armed: the caller armed ins_fail_sig and a check of its own has filed into it (the flat id pass)
     hipError_t insert_verified(const InsertIn& in, const uint8_t* digest, const uint8_t* r, int64_t count,
-                               InsertOut& out);
+                               InsertOut& out, bool fail_armed = false);
     hipError_t stage_sig(const uint8_t* digest, const uint8_t* r, int64_t count, const uint8_t** d_digest,
                          const uint8_t** d_r);
     // the same with Event.Hash and Event.Verify's digest computed here from the events' fields (host
@@ -152,6 +153,11 @@ class Engine {
     // other-parents, 32 bytes per event (read on a context with root ids only).
     hipError_t insert_bodies(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count, const uint8_t* op_id32,
                              uint8_t* out_id32, InsertOut& out);
+    // The same with every event's claimed id supplied (host, [count][32]): the ids are
+    // proven in one flat pass instead of computed level after level. out.code = INS_ID_MISMATCH at the
+    // first event whose claimed id is not its hash, behind the proven and accepted prefix.
+    hipError_t insert_bodies_claimed(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count,
+                                     const uint8_t* op_id32, const uint8_t* claimed_id32, InsertOut& out);
     // The same for a SyncResponse's wire events (hgx_wire.hip): ev.sp / ev.op hold the
     // host plan's parent descriptors (hgx_wire_plan.h), lo / woff / slots its windows. The window is
     // filled once against the resident events (not launched when n_resident == 0), every chunk's
@@ -208,6 +214,11 @@ class Engine {
                               BodyPlan& plan);
     hipError_t bodies_copy(const BodyPlan& plan, uint8_t* o_R, int32_t* o_ntx, int64_t* o_txi, int64_t* o_off,
                            uint8_t* o_bytes);
+    // hgx_save_bodies: the store is in gid order, so a gid range is a slice of each table. `count` entries
+    // from `lo` of the R rows (32 bytes each), the events' first slots (b_txi, E + 1 entries), the
+    // transaction offsets (b_off, T + 1 entries) or the arena's bytes, into host memory; returns when copied.
+    enum BodyTable { kBodyRows = 0, kBodySlots = 1, kBodyOffsets = 2, kBodyArena = 3 };
+    hipError_t bodies_read(BodyTable which, int64_t lo, int64_t count, void* dst);
     hipError_t bodies_gather(const int64_t* gids_host, const int64_t* gids_dev64, const int32_t* gids_dev32, int64_t m,
                              const BodyOut& out, int64_t* n_tx, int64_t* n_bytes, BodyFit* fit);
     // hgx_prune_to_frame on a keeping context, behind prune_stage and before anything is dropped: the
@@ -442,7 +453,8 @@ class Engine {
     hipError_t ensure_round_cap(int32_t need);
     hipError_t insert_impl(const InsertIn& in, int64_t count, InsertOut& out, const unsigned long long* fail_sig,
                            int commit_mode = kCommitAll);
-    // insert_bodies' chunk loop; wire: the parent columns carry window descriptors (insert_wire_bodies)
+    // insert_bodies' chunk loop; wire: the parent columns carry window descriptors (insert_wire_bodies);
+    // claimed: the flat id pass against these claimed ids in place of the level plan and k_ev_ids
     struct WireRun {
         const int32_t* win;   // the filled window (device)
         int64_t slots;
@@ -453,7 +465,7 @@ class Engine {
     };
     hipError_t insert_bodies_run(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count,
                                  const uint8_t* op_id32, uint8_t* out_id32, InsertOut& out, const WireRun* wire,
-                                 const SignOut* sign = nullptr);
+                                 const SignOut* sign = nullptr, const uint8_t* claimed = nullptr);
     hipError_t wipe_signing_keys();
     DBuf<uint8_t> sk_keys;   // [C][32] the private keys (HBM only: never saved, exported or stored with bodies)
     hipStream_t stream2 = nullptr;   // payload copies of insert_split (created on first use)

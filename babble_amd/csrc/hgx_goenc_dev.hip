@@ -409,6 +409,36 @@ k_ev_ids(const int32_t* __restrict__ wg_lo, const int32_t* __restrict__ wg_nl, c
     }
 }
 
+// The flat id pass (hgx_insert_event_bodies_claimed): the caller supplies every event's
+// claimed id, so no event waits for its parents' hashes. One lane per chunk event, no level plan, no
+// fence, no barrier: patch the parents' hex ids with the chunk's CLAIMED column as the in-chunk source
+// (resident parents from the store's id column, root codes from the root tables and op_rid, as in
+// k_ev_ids), hash the text into the separate computed column (other lanes read the claimed column, which
+// is never written), compare the 32 bytes. A difference files the chunk position in *first, the verified
+// insert's signature word (kInsIdWordCode in its low byte: at one position it sorts before Verify's
+// codes). By induction in gid order the smallest filed position m is exact and every event before it is
+// proven; ids computed behind m may rest on a wrong parent id and are dropped with the rejected tail.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
+k_ev_ids_claimed(int64_t m, const int64_t* __restrict__ sp, const int64_t* __restrict__ op,
+                 const int64_t* __restrict__ off, const int64_t* __restrict__ len, const int64_t* __restrict__ slot,
+                 int64_t base, const uint8_t* store_id, uint8_t* text, const uint8_t* claimed, uint8_t* __restrict__ ids,
+                 const int32_t* __restrict__ creator, RootIds rt, const uint8_t* op_rid, unsigned long long* first) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= m) return;
+    const int64_t o = off[k];
+    patch_parents(k, sp[k], op[k], o + slot[k], base, store_id, text, claimed, creator, rt, op_rid);
+    uint32_t h[8];
+    sha256_message<false>(text, o, len[k], 0, h);
+    const uint32_t* want = (const uint32_t*)(claimed + 32 * k);
+    uint32_t diff = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        ((uint32_t*)(ids + 32 * k))[j] = h[j];
+        diff |= h[j] ^ want[j];
+    }
+    if (diff) atomicMin(first, ((unsigned long long)k << 8) | (unsigned long long)kInsIdWordCode);
+}
+
 // What the signing id pass reads of a staged chunk (k_ev_ids' parameters)
 struct IdPass {
     const int32_t *wg_lo, *wg_nl, *loff, *pos;
@@ -565,15 +595,17 @@ struct EvScratch {
     int64_t *d_len = nullptr, *d_off = nullptr, *d_slot = nullptr, *d_blen = nullptr;
     uint8_t *d_ids = nullptr, *d_dig = nullptr;
     const uint8_t* d_op_rid = nullptr;   // the staged ids of HGX_ROOT_OTHER other-parents, or null
+    const uint8_t* d_claimed = nullptr;  // the staged claimed ids (the flat id pass), or null
     int64_t n_root_other = 0;            // the chunk's events with that code (counted when the column is staged)
 
     // Stage events [lo, hi) (m of them): columns, transactions, the parents' ids (json mode) or the
     // level plan (insert mode, base = gid of event lo), and on a context with root ids the Root.X flags
-    // and the ids of the HGX_ROOT_OTHER other-parents (op_rid, may be null), in ONE host-to-device copy.
+    // and the ids of the HGX_ROOT_OTHER other-parents (op_rid, may be null), and the claimed ids of the flat
+    // id pass (claimed, may be null), in ONE host-to-device copy.
     hipError_t stage(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t lo, int64_t hi, const uint8_t* keys_dev,
                      const uint8_t* keys_host, int32_t n_keys, const uint8_t* sp_id, const uint8_t* op_id, bool with_plan,
                      int64_t base, int32_t n_per_graph, hipStream_t s, const uint8_t* root_has_x = nullptr,
-                     const uint8_t* op_rid = nullptr) {
+                     const uint8_t* op_rid = nullptr, const uint8_t* claimed = nullptr) {
         const size_t m = (size_t)(hi - lo);
         const int64_t t0 = txi[(size_t)lo], t1 = txi[(size_t)hi];
         const size_t nt = (size_t)(t1 - t0);
@@ -591,11 +623,11 @@ struct EvScratch {
                                ev.s ? ev.s + 32 * lo : nullptr, ev.ntx + lo, nullptr, nullptr, nbytes ? ev.tx_bytes + b0 : nullptr,
                                keys_host, sp_id ? sp_id + 32 * lo : nullptr, op_id ? op_id + 32 * lo : nullptr, nullptr,
                                nullptr};
-        size_t bytes[19] = {4 * m, 8 * m, 8 * m, 8 * m, 8 * m, 32 * m, 32 * m, 4 * m, 8 * m, 8 * (nt + 1), nbytes,
+        size_t bytes[20] = {4 * m, 8 * m, 8 * m, 8 * m, 8 * m, 32 * m, 32 * m, 4 * m, 8 * m, 8 * (nt + 1), nbytes,
                             keys_host ? (size_t)65 * (size_t)n_keys : 0, sp_id ? 32 * m : 0, op_id ? 32 * m : 0,
-                            4 * nwg, 4 * nwg, 4 * nloff, with_plan ? 4 * m : 0, op_rid ? 32 * m : 0};
-        size_t o[19], total = 0;
-        for (int i = 0; i < 19; i++) {
+                            4 * nwg, 4 * nwg, 4 * nloff, with_plan ? 4 * m : 0, op_rid ? 32 * m : 0, claimed ? 32 * m : 0};
+        size_t o[20], total = 0;
+        for (int i = 0; i < 20; i++) {
             o[i] = total;
             // 16 spare bytes behind every column: the hash reader's aligned loads, and for tx_bytes
             // (o[10]) the shifted dword reads of k_body_append's copy_bytes, up to 7 bytes past the end
@@ -626,6 +658,7 @@ struct EvScratch {
             std::memcpy(h + o[18], op_rid + 32 * lo, 32 * m);
             for (int64_t k = lo; k < hi; k++) n_root_other += ev.op[k] == HGX_ROOT_OTHER;
         }
+        if (claimed) std::memcpy(h + o[19], claimed + 32 * lo, 32 * m);
         HGX_TRY(hipMemcpyAsync(in.p, h, total, hipMemcpyHostToDevice, s));
         uint8_t* d = in.p;
         cols.creator = (const int32_t*)(d + o[0]); cols.index = (const int64_t*)(d + o[1]);
@@ -636,6 +669,7 @@ struct EvScratch {
         cols.sp_id = sp_id ? d + o[12] : nullptr; cols.op_id = op_id ? d + o[13] : nullptr;
         cols.root_has_x = root_has_x;
         d_op_rid = op_rid ? d + o[18] : nullptr;
+        d_claimed = claimed ? d + o[19] : nullptr;
         d_wg_lo = (const int32_t*)(d + o[14]); d_wg_nl = (const int32_t*)(d + o[15]);
         d_loff = (const int32_t*)(d + o[16]); d_pos = (const int32_t*)(d + o[17]);
         // lengths, offsets (m + 1), slots, body lengths; ids and digests (16-byte aligned)
@@ -686,6 +720,15 @@ hipError_t Engine::sign_insert_bodies(const BodiesIn& ev, const std::vector<int6
     return insert_bodies_run(ev, txi, count, op_id32, out_id32, out, nullptr, &so);
 }
 
+// The flat route (hgx_insert_event_bodies_claimed): claimed_id32 (host, [count][32]) stands
+// for the ids of in-call parents, k_ev_ids_claimed proves it; the first wrong claimed id ends the call
+// with INS_ID_MISMATCH behind the proven prefix, unless that prefix has a failure of its own.
+hipError_t Engine::insert_bodies_claimed(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count,
+                                         const uint8_t* op_id32, const uint8_t* claimed_id32, InsertOut& out) {
+    if (!claimed_id32) return hipErrorInvalidValue;
+    return insert_bodies_run(ev, txi, count, op_id32, nullptr, out, nullptr, nullptr, claimed_id32);
+}
+
 // The wire route (hgx_insert_wire_bodies): the window of the resident parents is filled once, against
 // the events resident before the call; a later chunk's parents in an earlier chunk are final gids.
 hipError_t Engine::insert_wire_bodies(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count,
@@ -720,8 +763,9 @@ hipError_t Engine::insert_wire_bodies(const BodiesIn& ev, const std::vector<int6
 
 hipError_t Engine::insert_bodies_run(const BodiesIn& ev, const std::vector<int64_t>& txi, int64_t count,
                                      const uint8_t* op_id32, uint8_t* out_id32, InsertOut& out, const WireRun* wire,
-                                     const SignOut* sign) {
+                                     const SignOut* sign, const uint8_t* claimed) {
     if (sign && !sign_keys_set) return hipErrorNotReady;
+    if (claimed && (sign || wire)) return hipErrorInvalidValue;
     if (!ev_scratch) ev_scratch = new EvScratch();
     EvScratch& sc = *ev_scratch;
     int64_t done = 0;
@@ -749,7 +793,9 @@ hipError_t Engine::insert_bodies_run(const BodiesIn& ev, const std::vector<int64
             out.code = INS_BODY_CAPACITY;
             break;
         }
-        HGX_TRY(sc.stage(ev, txi, done, hi, pk_keys.p, nullptr, C, nullptr, nullptr, true, E, n, stream, rt.has_x, op_id32));
+        // (the flat pass needs no level plan: neither hgx_batch_levels nor the (graph, level) sort runs)
+        HGX_TRY(sc.stage(ev, txi, done, hi, pk_keys.p, nullptr, C, nullptr, nullptr, claimed == nullptr, E, n, stream,
+                         rt.has_x, op_id32, claimed));
         sc.cols.open_sig = sign ? 1 : 0;
         if (wire && wire->win)   // window descriptors -> gids, before the encoder reads the parent columns
             launch_wire_resolve(stream, m, const_cast<int64_t*>(sc.cols.sp), const_cast<int64_t*>(sc.cols.op), wire->win,
@@ -758,7 +804,15 @@ hipError_t Engine::insert_bodies_run(const BodiesIn& ev, const std::vector<int64
         HGX_TRY(sc.write(m, (size_t)bound, true, stream));
         const IdPass idp{sc.d_wg_lo, sc.d_wg_nl, sc.d_loff, sc.d_pos, sc.cols.sp, sc.cols.op, sc.d_off, sc.d_slot, E,
                          g_id.p, sc.text.p, sc.d_ids, sc.cols.creator, rt, sc.d_op_rid};
-        if (sign) {
+        if (claimed) {
+            // the verified insert's signature word, armed here: the mismatches and Verify's failures share it
+            if (ins_fail_sig.n < 1) HGX_TRY(ins_fail_sig.alloc(1));
+            HGX_TRY(hipMemsetAsync(ins_fail_sig.p, 0xFF, 8, stream));
+            hipLaunchKernelGGL(k_ev_ids_claimed, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, m, sc.cols.sp,
+                               sc.cols.op, (const int64_t*)sc.d_off, (const int64_t*)sc.d_len, (const int64_t*)sc.d_slot, E,
+                               (const uint8_t*)g_id.p, sc.text.p, sc.d_claimed, sc.d_ids, sc.cols.creator, rt, sc.d_op_rid,
+                               ins_fail_sig.p);
+        } else if (sign) {
             // a level's lanes stride over its events: the signer's workgroup is one wave whatever the width
             hipLaunchKernelGGL(k_ev_sign_ids, dim3((unsigned)sc.plan.wg_lo.size()), dim3(kSignBlock), 0, stream, idp, sc.d_len,
                                (const int64_t*)sc.d_blen, (const uint8_t*)sk_keys.p,
@@ -782,7 +836,9 @@ hipError_t Engine::insert_bodies_run(const BodiesIn& ev, const std::vector<int64
         in.creator = sc.cols.creator; in.index = sc.cols.index; in.sp = sc.cols.sp; in.op = sc.cols.op;
         in.ts = sc.cols.ts; in.hash = sc.d_ids; in.S = sc.cols.s; in.ntx = sc.cols.ntx; in.nil = nullptr;
         InsertOut co;
-        HGX_TRY(insert_verified(in, sc.d_dig, sc.cols.r, m, co));
+        HGX_TRY(insert_verified(in, sc.d_dig, sc.cols.r, m, co, claimed != nullptr));
+        // (a prefix cut by a word without a code: the flat pass's, which no check of the prefix came before)
+        if (claimed && co.code == INS_OK && co.accepted < m) co.code = INS_ID_MISMATCH;
         if (keep && co.accepted > 0) {   // the accepted prefix's R rows, slots, offsets and bytes (one launch)
             const int64_t t_hi = txi[(size_t)(done + co.accepted)];
             HGX_TRY(bodies_append(sc.cols.r, sc.cols.txi, sc.cols.tx_off, sc.cols.tx_bytes, co.accepted, t_hi - t_lo,

@@ -105,9 +105,15 @@ enum InsertCode {
     INS_PASSED_INDEX = 5, INS_SKIPPED_INDEX = 6, INS_INDEX_RANGE = 7,
     INS_BAD_SIG = 8, INS_BAD_KEY = 9,  // Event.Verify: invalid signature / creator key not a P-256 point
     INS_WIRE_HOLE = 10,                // hgx_insert_wire_bodies: a parent's window slot was never filled (a bug)
-    INS_BODY_CAPACITY = 11             // a keeping context (hgx_keep_bodies): the body store could not grow for a chunk
+    INS_BODY_CAPACITY = 11,            // a keeping context (hgx_keep_bodies): the body store could not grow for a chunk
+    INS_ID_MISMATCH = 12               // hgx_insert_event_bodies_claimed: the claimed id is not the event's hash
 };
-constexpr int64_t kWireHoleParent = -2;   // HGX_UNKNOWN_PARENT (include/hgx.h)
+// The low byte the flat id pass files with a mismatch's position in the signature word: below every
+// code, so at one position the mismatch wins the atomicMin against Verify's failure. The kernels read
+// the position alone; the host sees an accepted prefix short of the batch with code 0 and names it
+// INS_ID_MISMATCH.
+constexpr int kInsIdWordCode = 0;
+constexpr int64_t kWireHoleParent = -2;  // HGX_UNKNOWN_PARENT (include/hgx.h)
 
 // arguments of the round step (hgx_rounds.hip)
 struct RoundArgs {

@@ -335,6 +335,23 @@ class Hashgraph:
             raise
         return ids
 
+    def insert_bodies_claimed(self, cols: dict, ids, other_parent_id32=None, lo: int = 0, hi: Optional[int] = None) -> int:
+        """InsertEvent for events that come with their ids (hgx_insert_event_bodies_claimed): events
+        [lo, hi) of body_columns() and ids [len(cols), 32], their claimed ids. One flat hash pass on the
+        device proves every claimed id; Event.Verify and the insert follow as in insert_bodies. Returns
+        the number inserted. Raises HgxError on the first rejected event or the first claimed id that is
+        not its event's hash, with .inserted = events inserted before it."""
+        hi = len(cols["creator"]) if hi is None else hi
+        a, ev = _event_bodies_of(cols, lo, hi)
+        cl = np.ascontiguousarray(np.asarray(ids, np.uint8).reshape(-1, 32)[lo:hi])
+        assert cl.shape[0] == hi - lo
+        opi = None
+        if other_parent_id32 is not None:
+            opi = np.ascontiguousarray(np.asarray(other_parent_id32, np.uint8).reshape(-1, 32)[lo:hi])
+            assert opi.shape[0] == hi - lo
+        return self._insert_call(self.L.hgx_insert_event_bodies_claimed, C.byref(ev), ptr(cl),
+                                 None if opi is None else ptr(opi), hi - lo)
+
     def set_signing_keys(self, priv32):
         """The private keys Event.Sign uses here (hgx_set_signing_keys): C x 32 bytes (big-endian d),
         participant id order, 32 zero bytes = no key for that participant; None clears. Needs
@@ -495,6 +512,12 @@ class Hashgraph:
         """Checkpoint of the resident events (hgx_save; the BadgerStore's topological event log,
         badger_store.go:309-343). Format: include/hgx.h, babble_amd/checkpoint.py."""
         self._call(lambda ctx, e: self.L.hgx_save(ctx, os.fsencode(path), e))
+
+    def save_bodies(self, path: str):
+        """Checkpoint of a context that keeps its event bodies (hgx_save_bodies): a version-3 file with
+        every event's R and transactions, the roots' ids and the kept blocks' hashes. Bootstrap of such a
+        file proves every id and signature in it and, on a keeping context, restores the body store."""
+        self._call(lambda ctx, e: self.L.hgx_save_bodies(ctx, os.fsencode(path), e))
 
     def save_with_payloads(self, path: str, payloads: Sequence[bytes]):
         """Checkpoint with the caller's per-event bytes (hgx_save_ex), one entry per event

@@ -276,6 +276,26 @@ int32_t hgx_insert_event_bodies(hgx_ctx* ctx, const hgx_event_bodies* ev, int64_
  * byte for byte. */
 int32_t hgx_insert_event_bodies_ext(hgx_ctx* ctx, const hgx_event_bodies* ev, const uint8_t* other_parent_id32,
                                     int64_t count, uint8_t* out_id32, int64_t* n_inserted, hgx_error* err);
+/* hgx_insert_event_bodies_ext for events that arrive with their ids: a checkpoint,
+ * a Frame, or a Go Event out of a store, whose Body.Parents are hex strings. claimed_id32 (32 bytes per
+ * event, host memory) is every event's CLAIMED id. The texts are built with the parents' claimed ids
+ * (a parent below hgx_num_events from the store's id column, the root codes as in _ext), all of them are
+ * hashed in ONE flat pass, one lane per event, with no dependency order, and every hash is compared with
+ * the event's claimed id. If all agree every claimed id is the event's hash (induction in gid order: the
+ * first event with a wrong claimed id has parents whose claimed ids are right, so its text is its true
+ * text and its hash differs from the claim); hence the smallest mismatching position k is exact, events
+ * [0, k) are proven and go through Event.Verify and the insert, and everything computed behind k is
+ * dropped. Preconditions, refusals ("hgx_insert_event_bodies_claimed: <reason>"), the cut rule for
+ * events without a text, the internal chunks, the scratch bound (32 bytes more per event of a chunk on
+ * both sides; no level plan is built) and the resulting context state, body store included, are those of
+ * hgx_insert_event_bodies_ext on the same events. One more outcome: HGX_ERR_INVALID
+ * "hgx_insert_event_bodies_claimed: event <k>: the claimed id is not the event's hash", *n_inserted = k,
+ * events [0, k) resident with their proven ids. First failure inside a call: a failure of the proven
+ * prefix (its Go error: "Invalid signature", the parent and index checks) at a position j < k comes
+ * first; at the same position the mismatch wins. claimed_id32 == NULL is HGX_ERR_INVALID. */
+int32_t hgx_insert_event_bodies_claimed(hgx_ctx* ctx, const hgx_event_bodies* ev, const uint8_t* claimed_id32,
+                                        const uint8_t* other_parent_id32, int64_t count, int64_t* n_inserted,
+                                        hgx_error* err);
 /* Event.Sign on the device. hgx_set_signing_keys: C = graphs * n_participants
  * private keys of 32 bytes (big-endian d), participant id order; 32 zero bytes = this participant does
  * not sign here (a real node holds one key); NULL clears. Needs hgx_set_participant_keys first (a later
@@ -453,6 +473,40 @@ int32_t hgx_clear(hgx_ctx* ctx);
 int32_t hgx_save(hgx_ctx* ctx, const char* path, hgx_error* err);
 int32_t hgx_save_ex(hgx_ctx* ctx, const char* path, const int64_t* payload_off, const uint8_t* payload,
                     hgx_error* err);
+/* hgx_save_bodies: the checkpoint of a context that keeps its event bodies (hgx_keep_bodies; DESIGN.md
+ * section 3.17), a VERSION 3 file, written atomically like hgx_save. The header is version 2's with
+ * version = 3; the flags hold 2, 4 and 16 (bodies), never 8, and 1 when rooted. The sections are
+ * version 2's in the same order, with these additions:
+ *   behind the rooted section's per-graph kept state (rooted files only):
+ *     u8 has_x[C] | u8 has_y[C] | zero pad to 4 | u8 x_id[C][32] | u8 y_id[C][32]   (hgx_get_root_ids;
+ *       rows with has = 0 are zero; has_y equals root_y_is_event)
+ *     | i64 n_pairs | u8 pair_event[n_pairs][32] | u8 pair_parent[n_pairs][32]   (hgx_get_root_others,
+ *       sorted by event id; pair_event equals the Root.Others keys section)
+ *     | per graph, per kept block in order: u8 has_hash, 3 zero bytes, u8 hash[32]   (Block.Hash of the
+ *       blocks that outlived a prune)
+ *   behind the keys:
+ *     u8 sig_r[E][32] | i64 T | i64 tx_off[T+1] | u8 tx_bytes[tx_off[T]]   (T = sum of ntx; tx_off starts
+ *       at 0 and does not decrease; an event's transactions are consecutive entries, gid order)
+ *   | u64 FNV-1a of every preceding byte.
+ * The store is read in slices of bounded size (it is in gid order), so host memory beyond the per-event
+ * columns stays bounded. Refused with HGX_ERR_INVALID "hgx_save_bodies: <reason>": "bodies not known"
+ * (hgx_bodies_state != 1), "ids not known", "root ids not known" (rooted, before hgx_set_root_ids),
+ * "participant keys not set", chain- or row-sharded. hgx_save / hgx_save_ex keep writing version 2.
+ *
+ * hgx_bootstrap of a version-3 file trusts nothing in it. Pass 1 checks the checksum and every section
+ * with the context untouched (the refusals above, "unsupported flags", "root pairs and Root.Others keys
+ * disagree", "T is not the sum of ntx", "tx_off decreases", "size mismatch", ...). Pass 2 installs the
+ * roots, the kept state with its block hashes, the keys and the root ids (hgx_set_root_ids), then feeds the
+ * events in pieces to hgx_insert_event_bodies_claimed with the file's ids as the claimed ids (an
+ * HGX_ROOT_OTHER event's other-parent id is its pair's; without a pair the device's check fails it with
+ * "CheckOtherParent: Other-parent not known"), then hgx_run_consensus. So every id is proven to be its
+ * event's hash and every signature is verified, as the reference's Bootstrap does through InsertEvent. A
+ * replay failure returns its Go error, or HGX_ERR_INVALID "hgx_bootstrap: event <gid>: the file's id is
+ * not the event's hash", with the accepted prefix resident. On a context that called hgx_keep_bodies
+ * while empty the store grows once to the file's totals and ends complete with the file's bodies; on
+ * any other context the file is verified all the same and hgx_bodies_state stays 0. Afterwards the ids
+ * and the root ids are known. */
+int32_t hgx_save_bodies(hgx_ctx* ctx, const char* path, hgx_error* err);
 /* the file's checksum: 64-bit FNV-1a of `bytes` bytes (host function, no device) */
 uint64_t hgx_checksum(const void* data, int64_t bytes);
 int32_t hgx_bootstrap(hgx_ctx* ctx, const char* path, hgx_error* err);
