@@ -198,6 +198,11 @@ def lib():
     _sig(L, "hgx_read_wire_info", i32, [p, i32, i64, i32, i64, p, p, E])
     _sig(L, "hgx_diff_wire", i32, [p, i32, p, i64, p, i64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), E])
     _sig(L, "hgx_keep_bodies", i32, [p, i64, i64, E])
+    _sig(L, "hgx_keep_id_index", i32, [p, E])
+    _sig(L, "hgx_id_index_state", i32, [p, C.POINTER(C.c_int64), E])
+    _sig(L, "hgx_find_events", i32, [p, p, i64, p, E])
+    _sig(L, "hgx_insert_events_by_id", i32, [p, C.POINTER(hgx_event_bodies), p, p, p, p, i64, p, p,
+                                             C.POINTER(C.c_int64), E])
     _sig(L, "hgx_bodies_state", i32, [p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)])
     _sig(L, "hgx_get_event_bodies", i32, [p, p, i64, p, p, p, i64, p, i64, C.POINTER(C.c_int64),
                                           C.POINTER(C.c_int64), E])

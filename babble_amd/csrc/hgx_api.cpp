@@ -25,6 +25,7 @@
 #include "hgx_ckpt_host.h"
 #include "hgx_diff.h"
 #include "hgx_engine.h"
+#include "hgx_idindex.h"
 #include "hgx_wire_plan.h"
 
 namespace {
@@ -876,10 +877,12 @@ int32_t hgx_insert_events_verified_device(hgx_ctx* c, const hgx_events* ev, cons
 static int32_t insert_event_bodies_impl(hgx_ctx* c, const hgx_event_bodies* evb, const uint8_t* other_parent_id32,
                                         int64_t count, bool sign, uint8_t* out_r32, uint8_t* out_s32, uint8_t* out_id32,
                                         int64_t* n_inserted, hgx_error* err, bool claimed = false,
-                                        const uint8_t* claimed_id32 = nullptr) {
-    const char* fn = claimed ? "hgx_insert_event_bodies_claimed"
-                     : sign  ? "hgx_sign_insert_event_bodies"
-                             : "hgx_insert_event_bodies";
+                                        const uint8_t* claimed_id32 = nullptr, const char* by_id_fn = nullptr) {
+    // by_id_fn (hgx_insert_events_by_id): the claimed path under that call's name
+    const char* fn = by_id_fn ? by_id_fn
+                     : claimed ? "hgx_insert_event_bodies_claimed"
+                     : sign    ? "hgx_sign_insert_event_bodies"
+                               : "hgx_insert_event_bodies";
     const std::string who = std::string(fn) + ": ";
     auto bad = [&](const std::string& why) {
         set_err(err, HGX_ERR_INVALID, who + why);
@@ -928,7 +931,10 @@ static int32_t insert_event_bodies_impl(hgx_ctx* c, const hgx_event_bodies* evb,
         if (out.code == hgx::INS_OK) c->eng.ids_known = false;   // (unreachable: the event was stored without an id)
         out.accepted += ok_before;
     }
-    return finish_insert(c, out, n_inserted, err);
+    const int32_t rc = finish_insert(c, out, n_inserted, err);
+    if (by_id_fn && out.code == hgx::INS_ID_MISMATCH)   // the mismatch under the calling entry's name
+        set_err(err, rc, who + "event " + std::to_string(out.accepted) + ": the claimed id is not the event's hash");
+    return rc;
 }
 
 int32_t hgx_insert_event_bodies_ext(hgx_ctx* c, const hgx_event_bodies* evb, const uint8_t* other_parent_id32,
@@ -1708,6 +1714,8 @@ int32_t hgx_bootstrap(hgx_ctx* c, const char* path, hgx_error* err) {
     // a version-1 file carries no ids: its Root.Others codes were checked when the events were
     // first inserted; a version-2 rooted file brings the keys and the ids, so they are checked again
     c->eng.others_trust = (flags & kCkRooted) && !have_ids;
+    // (an id-less file: the id column is not to be indexed, hgx_keep_id_index)
+    if (!have_ids && c->eng.idx_kept) c->eng.ids_known = false;
     int32_t rc = hgx_insert_events(c, &ev, E, &inserted, err);
     c->eng.others_trust = false;
     if (!have_ids) c->eng.ids_known = false;
@@ -3007,6 +3015,107 @@ int32_t hgx_keep_bodies(hgx_ctx* c, int64_t tx_hint, int64_t bytes_hint, hgx_err
     }
     if (e != hipSuccess) return dev_err(err, e, "hgx_keep_bodies");
     return ok(err);
+}
+
+// ---- the event-id index -------------------------------------------------
+static int32_t idx_corrupt(hgx_error* err, const char* who) {
+    set_err(err, HGX_ERR_DEVICE, std::string(who) + ": id index corrupt");
+    return HGX_ERR_DEVICE;
+}
+
+int32_t hgx_keep_id_index(hgx_ctx* c, hgx_error* err) {
+    auto bad = [&](const char* why) {
+        set_err(err, HGX_ERR_INVALID, std::string("hgx_keep_id_index: ") + why);
+        return (int32_t)HGX_ERR_INVALID;
+    };
+    if (!c) return bad("bad arguments");
+    if (c->G > 1) return bad("not available on a batched context");
+    if (c->grp) return bad("not available on a chain-sharded context");
+    if (c->shard_world > 1) return bad("not available on a row-sharded context");
+    if (c->eng.cap >= hgx::kIdxMaxCapacity) return bad("capacity beyond 2^31 - 1 events");
+    if (c->eng.idx_kept) return ok(err);
+    DeviceGuard dg(c);
+    const hipError_t e = c->eng.idx_keep();
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        set_err(err, HGX_ERR_DEVICE, "hgx_keep_id_index: out of device memory");
+        return HGX_ERR_DEVICE;
+    }
+    if (e != hipSuccess) return dev_err(err, e, "hgx_keep_id_index");
+    return ok(err);
+}
+
+int32_t hgx_id_index_state(hgx_ctx* c, int64_t out[5], hgx_error* err) {
+    if (!c || !out) {
+        set_err(err, HGX_ERR_INVALID, "hgx_id_index_state: bad arguments");
+        return HGX_ERR_INVALID;
+    }
+    DeviceGuard dg(c);
+    bool corrupt = false;
+    int64_t st[5] = {};
+    const hipError_t e = c->eng.idx_state(st, &corrupt);
+    if (e != hipSuccess) return dev_err(err, e, "hgx_id_index_state");
+    if (corrupt) return idx_corrupt(err, "hgx_id_index_state");
+    std::memcpy(out, st, sizeof(st));
+    return ok(err);
+}
+
+int32_t hgx_find_events(hgx_ctx* c, const uint8_t* id32, int64_t count, int64_t* out_gid, hgx_error* err) {
+    auto bad = [&](const char* why) {
+        set_err(err, HGX_ERR_INVALID, std::string("hgx_find_events: ") + why);
+        return (int32_t)HGX_ERR_INVALID;
+    };
+    if (!c || count < 0 || (count > 0 && (!id32 || !out_gid))) return bad("bad arguments");
+    if (!c->eng.idx_kept) return bad("id index not kept");
+    if (!c->eng.ids_known) return bad("ids not known (the context holds events inserted without their ids)");
+    if (count == 0) return ok(err);
+    DeviceGuard dg(c);
+    std::vector<int64_t> got((size_t)count);   // (the caller's array stays untouched unless the call succeeds)
+    bool corrupt = false;
+    const hipError_t e = c->eng.idx_find(id32, count, got.data(), &corrupt);
+    if (e != hipSuccess) return dev_err(err, e, "hgx_find_events");
+    if (corrupt) return idx_corrupt(err, "hgx_find_events");
+    std::memcpy(out_gid, got.data(), (size_t)count * 8);
+    return ok(err);
+}
+
+// InsertEvent for Go Events as they are: Body.Parents as ids. The parents are resolved on the device
+// (Engine::idx_resolve), then the call is hgx_insert_event_bodies_claimed on the resolved columns.
+int32_t hgx_insert_events_by_id(hgx_ctx* c, const hgx_event_bodies* evb, const uint8_t* claimed_id32,
+                                const uint8_t* self_parent_id32, const uint8_t* other_parent_id32,
+                                const uint8_t* parent_flags, int64_t count, int64_t* out_self_parent,
+                                int64_t* out_other_parent, int64_t* n_inserted, hgx_error* err) {
+    const char* fn = "hgx_insert_events_by_id";
+    auto bad = [&](const char* why) {
+        set_err(err, HGX_ERR_INVALID, std::string(fn) + ": " + why);
+        return (int32_t)HGX_ERR_INVALID;
+    };
+    if (n_inserted) *n_inserted = 0;
+    if (!c || !evb || count < 0 || !claimed_id32 || !parent_flags || (count > 0 && !evb->creator))
+        return bad("bad arguments");
+    if (!c->eng.idx_kept) return bad("id index not kept");
+    if (!c->eng.ids_known) return bad("ids not known (the context holds events inserted without their ids)");
+    int need = 0;
+    for (int64_t k = 0; k < count; k++) need |= parent_flags[k];
+    if (((need & 1) && !self_parent_id32) || ((need & 2) && !other_parent_id32)) return bad("null parent id column");
+    std::vector<int64_t> sp((size_t)count), op((size_t)count);
+    if (count > 0) {
+        DeviceGuard dg(c);
+        bool corrupt = false;
+        const hipError_t e = c->eng.idx_resolve(claimed_id32, self_parent_id32, other_parent_id32, parent_flags,
+                                                evb->creator, count, sp.data(), op.data(), &corrupt);
+        if (e != hipSuccess) return dev_err(err, e, fn);
+        if (corrupt) return idx_corrupt(err, fn);
+    }
+    hgx_event_bodies ev = *evb;
+    ev.self_parent = sp.data();
+    ev.other_parent = op.data();
+    // (other_parent_id32 doubles as _ext's column: it is read for HGX_ROOT_OTHER events only)
+    const int32_t rc = insert_event_bodies_impl(c, &ev, other_parent_id32, count, false, nullptr, nullptr, nullptr,
+                                                n_inserted, err, true, claimed_id32, fn);
+    if (out_self_parent && count > 0) std::memcpy(out_self_parent, sp.data(), (size_t)count * 8);
+    if (out_other_parent && count > 0) std::memcpy(out_other_parent, op.data(), (size_t)count * 8);
+    return rc;
 }
 
 int32_t hgx_bodies_state(hgx_ctx* c, int64_t* n_events, int64_t* n_tx, int64_t* n_bytes) {

@@ -687,11 +687,16 @@ hipError_t Engine::insert_verified(const InsertIn& in, const uint8_t* digest, co
         launch_insert_sig_first(stream, count, C, in.creator, pk_out.p, ins_fail_sig.p);
         HGX_TRY(hipGetLastError());
     }
-    return insert_impl(in, count, out, count > 0 ? ins_fail_sig.p : nullptr);
+    HGX_TRY(insert_impl(in, count, out, count > 0 ? ins_fail_sig.p : nullptr));
+    return idx_kept ? idx_append() : hipSuccess;   // (the body paths' chunks: the id index follows each)
 }
 
 hipError_t Engine::insert(const InsertIn& in, int64_t count, InsertOut& out) {
-    return insert_impl(in, count, out, nullptr);
+    HGX_TRY(insert_impl(in, count, out, nullptr));
+    // the id index follows the commit in a launch of its own (nothing on a context that keeps none, or
+    // whose ids are not known). A split insert (hgx_insert_and_run) does not pass here: its events are
+    // indexed by the next call that goes through here or that reads the index.
+    return idx_kept ? idx_append() : hipSuccess;
 }
 
 hipError_t Engine::insert_split_begin(const HostCols& hc, int64_t count, InsertOut& out) {
@@ -898,6 +903,7 @@ hipError_t Engine::clear() {
     ids_known = true;
     pipe_ready = false;
     HGX_TRY(bodies_reset());   // (nothing queued on a context that keeps no bodies)
+    HGX_TRY(idx_zero());       // (nor on one that keeps no id index)
     return hipStreamSynchronize(stream);
 }
 

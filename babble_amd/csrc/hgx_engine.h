@@ -723,6 +723,33 @@ class Engine {
     struct Open { int k; size_t e0; double bytes; int64_t count; };
     std::vector<Open> kopen;
     size_t kev_used = 0;
+
+   public:
+    // The event-id index (hgx_keep_id_index, hgx_idindex.hip / hgx_idindex.h): an
+    // open-addressing table over g_id, kept behind every insert() / insert_verified() that leaves ids_known
+    // true (idx_append: one launch over the events not yet indexed, [idx_done, E); the lookups run it
+    // first, which covers a split insert), emptied by clear() and so rebuilt by a prune's or a
+    // bootstrap's re-insert. It is valid exactly while ids_known. Nothing below is
+    // allocated or launched on a context that never called idx_keep.
+    hipError_t idx_keep();
+    hipError_t idx_zero();
+    hipError_t idx_append();
+    // out: hgx_id_index_state's five fields; *corrupt: a probe met no empty slot (a bug, or a table
+    // overwritten from outside)
+    hipError_t idx_state(int64_t out[5], bool* corrupt);
+    hipError_t idx_find(const uint8_t* id32, int64_t m, int64_t* out_gid, bool* corrupt);
+    // hgx_insert_events_by_id: the batch's parents' ids (host columns; sp_id32 / op_id32 may be null when
+    // no flag names them) resolved to gids and root codes in out_sp / out_op (host, count entries each)
+    hipError_t idx_resolve(const uint8_t* claimed_id32, const uint8_t* sp_id32, const uint8_t* op_id32,
+                           const uint8_t* flags, const int32_t* creator, int64_t count, int64_t* out_sp, int64_t* out_op,
+                           bool* corrupt);
+    bool idx_kept = false;
+    uint64_t idx_slots = 0;
+    int64_t idx_done = 0;      // events [0, idx_done) are in the table
+    DBuf<uint64_t> idx_tab;    // [idx_slots]
+    DBuf<uint64_t> idx_st;     // the status block: the sticky corrupt flag and the statistics
+    DBuf<uint8_t> idx_buf;     // scratch of a find or a resolve (queries, the batch's table and columns)
+    hipError_t idx_read_flag(bool* corrupt);
 };
 
 }  // namespace hgx

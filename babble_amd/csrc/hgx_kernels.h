@@ -459,4 +459,36 @@ void launch_wire_window(hipStream_t s, const WireWinArgs& a);
 void launch_wire_resolve(hipStream_t s, int64_t m, int64_t* sp, int64_t* op, const int32_t* win, int64_t slots,
                          unsigned long long* fail);
 
+// The event-id index (hgx_idindex.hip; the table's contract is hgx_idindex.h). tab holds
+// `slots` 8-byte words, rows is the id column the values index (g_id, or a batch's claimed ids), st the
+// index's status block: st[0] is raised, and stays raised, when a probe met no empty slot within `slots`
+// steps or a word named no row; st[1..3] take the statistics.
+// rows [first, first + count) claim their slots (value = the row's number)
+void launch_idx_insert(hipStream_t s, uint64_t* tab, uint64_t slots, const uint8_t* rows, int64_t first, int64_t count,
+                       uint64_t* st);
+// out[k] = the lowest gid below E whose id row equals q[k] (32 bytes each), or -1
+void launch_idx_find(hipStream_t s, const uint64_t* tab, uint64_t slots, const uint8_t* rows, int64_t E, const uint8_t* q,
+                     int64_t m, int64_t* out, uint64_t* st);
+// st[1] += entries, st[2] += the sum of (slot - home) mod slots, st[3] += entries below their home slot
+void launch_idx_stats(hipStream_t s, const uint64_t* tab, uint64_t slots, const uint8_t* rows, int64_t E, uint64_t* st);
+// hgx_insert_events_by_id: the parents' ids of a batch -> gids and root codes (the rules are hgx.h's)
+struct IdxResolveArgs {
+    const uint64_t* tab;       // the resident table over g_id rows [0, E)
+    uint64_t slots;
+    const uint8_t* g_id;
+    int64_t E;
+    const uint64_t* btab;      // the batch's scratch table over the claimed ids (value = position)
+    uint64_t bslots;
+    const uint8_t* claimed;    // [count][32]
+    int64_t count;
+    const uint8_t *sp_id, *op_id;   // [count][32], read where the flag's bit is set
+    const uint8_t* flags;      // bit 0: self-parent present, bit 1: other-parent present
+    const int32_t* creator;
+    int C;
+    const uint8_t* root_tab;   // x_id [C][32] | y_id [C][32] | has_x [C] | has_y [C]; null: no root ids
+    int64_t *out_sp, *out_op;
+    uint64_t* st;               // [0] the sticky corrupt flag
+};
+void launch_idx_resolve(hipStream_t s, const IdxResolveArgs& a);
+
 }  // namespace hgx

@@ -352,6 +352,56 @@ class Hashgraph:
         return self._insert_call(self.L.hgx_insert_event_bodies_claimed, C.byref(ev), ptr(cl),
                                  None if opi is None else ptr(opi), hi - lo)
 
+    # ------------------------------------------------------------------ the event-id index
+    def KeepIdIndex(self):
+        """hgx_keep_id_index: from here on the context keeps an index of its events' ids in device memory
+        (16 to 32 bytes per event of capacity), built now from the events it already holds. Idempotent."""
+        self._call(lambda ctx, e: self.L.hgx_keep_id_index(ctx, e))
+
+    def IdIndexState(self) -> dict:
+        """hgx_id_index_state: kept (0 off, 1 valid, 2 kept but invalid: ids not known), slots, entries,
+        total_displacement (sum of (slot - home) mod slots) and wrapped (entries below their home slot)."""
+        out = (C.c_int64 * 5)()
+        self._call(lambda ctx, e: self.L.hgx_id_index_state(ctx, out, e))
+        return dict(zip(("kept", "slots", "entries", "total_displacement", "wrapped"), (int(x) for x in out)))
+
+    def FindEvents(self, ids) -> np.ndarray:
+        """hgx_find_events: Store.GetEvent's lookup for a batch of 32-byte ids [m, 32]: each id's gid, or
+        -1 where no resident event has it (the lowest gid where several do)."""
+        q = np.ascontiguousarray(np.asarray(ids, np.uint8).reshape(-1, 32))
+        out = np.full(q.shape[0], -1, np.int64)
+        self._call(lambda ctx, e: self.L.hgx_find_events(ctx, ptr(q), q.shape[0], ptr(out), e))
+        return out
+
+    def insert_events_by_id(self, cols: dict, ids, sp_ids, op_ids, flags, lo: int = 0, hi: Optional[int] = None):
+        """hgx_insert_events_by_id: insert_bodies_claimed for events whose parents are given as ids: events
+        [lo, hi) of body_columns() (their sp / op columns are not read), ids / sp_ids / op_ids
+        [len(cols), 32] and flags [len(cols)] (bit 0: a self-parent, bit 1: an other-parent; sp_ids / op_ids
+        may be None where no flag names them). Returns (n_inserted, sp, op), the parents as the device
+        resolved them. Raises HgxError as insert_bodies_claimed does, with .inserted, .sp and .op."""
+        hi = len(cols["creator"]) if hi is None else hi
+        m = hi - lo
+        a, ev = _event_bodies_of(cols, lo, hi)
+
+        def rows(x):
+            if x is None:
+                return None
+            r = np.ascontiguousarray(np.asarray(x, np.uint8).reshape(-1, 32)[lo:hi])
+            assert r.shape[0] == m
+            return r
+        cl, spi, opi = rows(ids), rows(sp_ids), rows(op_ids)
+        fl = np.ascontiguousarray(np.asarray(flags, np.uint8)[lo:hi])
+        assert fl.shape[0] == m
+        sp, op = np.zeros(m, np.int64), np.zeros(m, np.int64)
+        try:
+            n = self._insert_call(self.L.hgx_insert_events_by_id, C.byref(ev), ptr(cl),
+                                  None if spi is None else ptr(spi), None if opi is None else ptr(opi), ptr(fl), m,
+                                  ptr(sp), ptr(op))
+        except HgxError as e:
+            e.sp, e.op = sp, op
+            raise
+        return n, sp, op
+
     def set_signing_keys(self, priv32):
         """The private keys Event.Sign uses here (hgx_set_signing_keys): C x 32 bytes (big-endian d),
         participant id order, 32 zero bytes = no key for that participant; None clears. Needs

@@ -42,7 +42,9 @@ extern "C" {
                                  (hgx_get_event_bodies, hgx_block_transactions, hgx_get_block_hash,
                                  hgx_block_hash_batch, hgx_diff_wire_bodies), and with the signer
                                  (hgx_p256_sign_batch, hgx_p256_public_keys, hgx_set_signing_keys,
-                                 hgx_sign_insert_event_bodies):
+                                 hgx_sign_insert_event_bodies), and with the event-id index
+                                 (hgx_keep_id_index, hgx_id_index_state, hgx_find_events,
+                                 hgx_insert_events_by_id):
                                  purely additive, no existing entry or structure changed)
                               6: hgx_host_alloc / hgx_host_free (page-locked caller buffers);
                               5: hgx_events_packed (hgx_insert_events_packed, hgx_insert_and_run_packed,
@@ -700,6 +702,66 @@ typedef struct {
  * (hgx_events32 / packed inserts: the other columns still work there). */
 int32_t hgx_diff_wire(hgx_ctx* ctx, int32_t graph, const int32_t* known, int64_t sync_limit,
                       hgx_wire_out* out, int64_t cap, int64_t* count, int32_t* over_limit, hgx_error* err);
+
+/* ---- the event-id index --------------------------------- */
+/* Opt in: from here on the context keeps an index of its events' ids in device memory, so that a caller
+ * who addresses events by hash (Store.GetEvent, Body.Parents) needs no table of its own. Idempotent; on a
+ * context that already holds events with known ids the index is built from them in one launch.
+ * The table: open addressing over the id column, slots = the smallest power of two >= 2 x the context's
+ * capacity (load <= 0.5), one 8-byte word per slot, 0 = empty, else (tag << 32) | (gid + 1); home slot =
+ * id bytes 0..7 as a little-endian u64 masked with slots - 1, tag = id bytes 8..11 as a little-endian
+ * u32, linear probing by +1 with wrap-around; a match needs the tag and all 32 bytes of the event's id.
+ * Memory: 8 bytes per slot, so 16 bytes per event of capacity (up to 32 at the worst rounding): 256 MiB
+ * at a capacity of 10 M events. Upkeep: every insert that brings ids (hgx_insert_events* with a hash
+ * column, the body paths chunk by chunk, the wire paths, hgx_bootstrap with ids) adds its accepted events
+ * in one more launch behind its commit (the split insert of a large hgx_insert_and_run batch: with the next insert
+ * or lookup); hgx_clear and hgx_reset empty the table; hgx_prune_to_frame and
+ * hgx_bootstrap empty it and rebuild it under the new gids. An insert without ids (hgx_events32 / packed,
+ * an id-less bootstrap) leaves the index kept but invalid: the lookups refuse with "ids not known" until
+ * hgx_clear, hgx_reset or a bootstrap with ids. The index is never written to a checkpoint (it can be
+ * derived); the keep flag survives all of the above. HGX_ERR_INVALID "hgx_keep_id_index: <reason>": NULL
+ * ctx, a batched (G > 1), chain-sharded or row-sharded context. HGX_ERR_DEVICE when the table cannot be
+ * allocated: the index stays off. A context that never called hgx_keep_id_index allocates nothing for it
+ * and launches no kernel of it. */
+int32_t hgx_keep_id_index(hgx_ctx* ctx, hgx_error* err);
+/* out = {kept (0 off, 1 valid, 2 kept but invalid), slots, entries, total_displacement, wrapped}:
+ * total_displacement = the sum over entries of (slot - home) mod slots, wrapped = the entries stored at a
+ * slot below their home slot. Both depend on the set of ids alone, not on the order the device inserted
+ * them in. Computed by a reduction on request (entries and the two sums are 0 unless kept = 1). */
+int32_t hgx_id_index_state(hgx_ctx* ctx, int64_t out[5], hgx_error* err);
+/* Store.GetEvent's lookup for `count` ids (host memory, 32 bytes each): out_gid[k] = the gid of the
+ * resident event with id k, or -1. Where several resident events have one id (the wide insert takes
+ * hashes on trust) the lowest gid. count = 0 is HGX_OK. HGX_ERR_INVALID "hgx_find_events: <reason>": bad
+ * arguments, "id index not kept", "ids not known ..."; out_gid is written on HGX_OK only.
+ * HGX_ERR_DEVICE "hgx_find_events: id index corrupt" when a probe met no empty slot (a bug). */
+int32_t hgx_find_events(hgx_ctx* ctx, const uint8_t* id32, int64_t count, int64_t* out_gid, hgx_error* err);
+/* InsertEvent for Go Events as they are: hgx_insert_event_bodies_claimed whose parents come as ids.
+ * ev->self_parent / ev->other_parent are ignored and may be NULL. parent_flags[k] bit 0 / bit 1: event k
+ * has a self-parent / an other-parent; a clear bit is Go's "" and that id row is not read. The device
+ * resolves every parent in two launches (a scratch table of the batch's claimed ids, 2 x count rounded up
+ * to a power of two slots; then a probe of the resident index and of that table), the resolved columns
+ * come back (16 bytes per event of the batch), and the call continues exactly as
+ * hgx_insert_event_bodies_claimed on them with other_parent_id32 as its id column.
+ *   self-parent   absent: -1; on a context with root ids whose creator's root has an X:
+ *                 HGX_UNKNOWN_PARENT (the text would print Root.X; Go fails CheckSelfParent there).
+ *                 present: the resident gid; else the LOWEST EARLIER batch position j < k whose claimed
+ *                 id equals it, as gid hgx_num_events + j; else -1 if it is the creator's Root.X id; else
+ *                 HGX_UNKNOWN_PARENT.
+ *   other-parent  absent: -1. present: resident, or an earlier batch position, as above; else with root
+ *                 ids HGX_ROOT_Y when it is the creator's Root.Y id and the event's self-parent string
+ *                 equals the root's X (both "" counts; hashgraph.go:434), otherwise HGX_ROOT_OTHER (the
+ *                 device's Root.Others check then decides); without root ids HGX_UNKNOWN_PARENT.
+ * A resident match wins over a batch match; a parent at the same or a later batch position is unknown.
+ * out_self_parent / out_other_parent (count entries, each may be NULL) receive the resolved codes of the
+ * whole batch. Results, Go error strings, first-failure order, *n_inserted, the body store and the
+ * context's state equal hgx_insert_event_bodies_claimed's on the same events with those codes; the error
+ * prefix is "hgx_insert_events_by_id: ". Further refusals, nothing changed: "id index not kept", "ids not
+ * known ...", NULL claimed_id32 or parent_flags, a NULL parent id column that some flag needs. Raw
+ * 32-byte ids only. Device scratch: 117 bytes per event of the batch plus its table (16 to 32). */
+int32_t hgx_insert_events_by_id(hgx_ctx* ctx, const hgx_event_bodies* ev, const uint8_t* claimed_id32,
+                                const uint8_t* self_parent_id32, const uint8_t* other_parent_id32,
+                                const uint8_t* parent_flags, int64_t count, int64_t* out_self_parent,
+                                int64_t* out_other_parent, int64_t* n_inserted, hgx_error* err);
 
 /* ---- the resident body store ---------------------------- */
 /* Opt in: from here on the body paths (hgx_insert_event_bodies, _ext, hgx_insert_wire_bodies) keep every
