@@ -82,6 +82,27 @@ class hgx_wire_body_out(C.Structure):
                 ("bytes_cap", C.c_int64)]
 
 
+# hgx_frame_out in declaration order: (name, numpy dtype and row shape) for an array, None for a capacity
+FRAME_OUT_FIELDS = (("root_index", (np.int32, ())), ("root_round", (np.int32, ())), ("root_x_id32", (np.uint8, (32,))),
+                    ("root_has_x", (np.int32, ())), ("root_y_id32", (np.uint8, (32,))), ("root_has_y", (np.int32, ())),
+                    ("others_event_id32", (np.uint8, (32,))), ("others_parent_id32", (np.uint8, (32,))),
+                    ("others_cap", None),
+                    ("gid", (np.int64, ())), ("creator", (np.int32, ())), ("index", (np.int64, ())),
+                    ("timestamp_ns", (np.int64, ())), ("ntx", (np.int32, ())), ("self_parent", (np.int64, ())),
+                    ("other_parent", (np.int64, ())), ("id32", (np.uint8, (32,))), ("sig_s", (np.uint8, (32,))),
+                    ("self_parent_id32", (np.uint8, (32,))), ("other_parent_id32", (np.uint8, (32,))),
+                    ("parent_flags", (np.uint8, ())), ("events_cap", None),
+                    ("sig_r", (np.uint8, (32,))), ("tx_off", (np.int64, ())), ("tx_cap", None),
+                    ("tx_bytes", (np.uint8, ())), ("bytes_cap", None))
+FRAME_ROOT_COLUMNS = tuple(nm for nm, _ in FRAME_OUT_FIELDS[:6])
+FRAME_OTHERS_COLUMNS = tuple(nm for nm, _ in FRAME_OUT_FIELDS[6:8])
+FRAME_EVENT_COLUMNS = tuple(nm for nm, _ in FRAME_OUT_FIELDS[9:21]) + ("sig_r",)
+
+
+class hgx_frame_out(C.Structure):
+    _fields_ = [(nm, C.c_int64 if spec is None else C.c_void_p) for nm, spec in FRAME_OUT_FIELDS]
+
+
 def ptr(a: np.ndarray):
     assert a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(C.c_void_p)
@@ -252,6 +273,8 @@ def lib():
     _sig(L, "hgx_set_commit_callback", i32, [p, C.c_void_p, p])
     _sig(L, "hgx_get_frame", i32, [p, p, i64, p, p, p, p, p, p, p, i64, p, p])
     _sig(L, "hgx_prune_to_frame", i32, [p, p, i64, C.POINTER(C.c_int64), E])
+    _sig(L, "hgx_get_frame_bodies", i32, [p, C.POINTER(hgx_frame_out), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), E])
     _sig(L, "hgx_get_root_ids", i32, [p, i32, p, C.POINTER(C.c_int32), p, C.POINTER(C.c_int32), E])
     _sig(L, "hgx_get_root_others", i32, [p, p, p, i64, C.POINTER(C.c_int64), E])
     _sig(L, "hgx_set_root_ids", i32, [p, p, p, p, p, p, p, i64, E])

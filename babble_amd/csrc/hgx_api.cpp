@@ -1924,6 +1924,100 @@ static const std::array<uint8_t, 64>* find_root_other(const hgx_ctx* c, const ui
     return it != c->root_others.end() && std::memcmp(it->data(), key32, 32) == 0 ? &*it : nullptr;
 }
 
+// The frame's cut and its roots' Index and Round, for hgx_prune_to_frame and hgx_get_frame_bodies:
+// cut[p] = the smallest kept Index of chain p (INT32_MAX: the chain has no event and keeps its
+// root), *kept = the frame's events. Round(Root.X) comes from the round boundaries; -1 for an X
+// outside the store or not yet divided, as hgx_get_frame has it. False: the round tables and the
+// chains disagree.
+static bool frame_cut(const hgx_ctx* c, int32_t lcr, std::vector<int32_t>& cut, std::vector<int32_t>& ri,
+                      std::vector<int32_t>& rr, int64_t* kept) {
+    const int C = c->C;
+    cut.assign((size_t)C, 0x7FFFFFFF);
+    ri = c->root_index;
+    rr = c->root_round;
+    *kept = 0;
+    const int32_t R = c->rh.R;
+    for (int p = 0; p < C; p++) {
+        const int32_t len = c->chain_len[(size_t)p];
+        if (len == 0) continue;   // LastFrom is the Root: it stays
+        int32_t k = len - 1;
+        if (lcr < R && c->rh.wflag[(size_t)lcr * C + p] == 2) k = c->rh.bm[(size_t)lcr * C + p];
+        if (k < 0 || k >= len) return false;
+        cut[(size_t)p] = c->chain_base[(size_t)p] + k;
+        *kept += len - k;
+        ri[(size_t)p] = cut[(size_t)p] - 1;
+        int32_t round = -1;
+        if (k > 0 && k - 1 < c->eng.len_div(p)) {
+            int32_t lo = 0, hi = R;   // the last r with bm[r] <= k - 1 (bm rows do not decrease)
+            while (lo < hi) {
+                const int32_t mid = (lo + hi) / 2;
+                if (c->rh.bm[(size_t)mid * C + p] <= k - 1) lo = mid + 1; else hi = mid;
+            }
+            round = lo - 1;
+        }
+        rr[(size_t)p] = round;
+    }
+    return true;
+}
+
+// The frame's roots as ids, from what prune_stage read back and the current roots' host tables: the
+// one place that resolves a parent stored as a code (k_prune_roots writes a zero row for it).
+struct FrameRoots {
+    std::vector<uint8_t> y_ext, x_id, y_id, has_x, has_y;
+    std::vector<std::array<uint8_t, 64>> others;   // (event id, other-parent id) sorted by event id
+    bool rooted = false, ids_ok = false;           // ids_ok: every id above is known
+};
+static void frame_roots(const hgx_ctx* c, const hgx::Engine::PruneOut& po, const std::vector<int32_t>& rr, FrameRoots& fr) {
+    const int C = c->C;
+    fr.y_ext = c->root_y_ext;
+    fr.rooted = false;
+    for (int p = 0; p < C; p++) {
+        if (c->chain_len[(size_t)p] > 0) fr.y_ext[(size_t)p] = po.root_op[(size_t)p] != -1 ? 1 : 0;
+        if (rr[(size_t)p] >= 0 || fr.y_ext[(size_t)p]) fr.rooted = true;
+    }
+    bool ids_ok = c->root_ids_known;
+    fr.x_id = c->root_x_id; fr.y_id = c->root_y_id; fr.has_x = c->root_has_x; fr.has_y = c->root_has_y;
+    fr.others.assign((size_t)po.n_others, std::array<uint8_t, 64>());
+    for (int64_t j = 0; j < po.n_others; j++) {
+        std::array<uint8_t, 64>& o = fr.others[(size_t)j];
+        std::memcpy(o.data(), po.oth_key.data() + 32 * j, 32);
+        if (po.oth_op[(size_t)j] >= 0) {
+            std::memcpy(o.data() + 32, po.oth_pid.data() + 32 * j, 32);
+        } else {   // HGX_ROOT_OTHER before: the entry is carried over
+            const std::array<uint8_t, 64>* old = ids_ok ? find_root_other(c, o.data()) : nullptr;
+            if (old) std::memcpy(o.data() + 32, old->data() + 32, 32);
+            else { std::memset(o.data() + 32, 0, 32); ids_ok = false; }
+        }
+    }
+    std::sort(fr.others.begin(), fr.others.end(), [](const std::array<uint8_t, 64>& a, const std::array<uint8_t, 64>& b) {
+        return std::memcmp(a.data(), b.data(), 32) < 0;
+    });
+    for (int p = 0; p < C && ids_ok; p++) {
+        if (c->chain_len[(size_t)p] == 0) continue;   // the whole root stays
+        const uint8_t* ids = po.root_ids.data() + 96 * (size_t)p;
+        const int32_t sp = po.root_sp[(size_t)p], op = po.root_op[(size_t)p];
+        if (sp >= 0) {
+            std::memcpy(fr.x_id.data() + 32 * (size_t)p, ids + 32, 32);
+            fr.has_x[(size_t)p] = 1;
+        }   // -1: the old Root.X stays
+        if (op >= 0) {
+            std::memcpy(fr.y_id.data() + 32 * (size_t)p, ids + 64, 32);
+            fr.has_y[(size_t)p] = 1;
+        } else if (op == -1) {
+            fr.has_y[(size_t)p] = 0;
+        } else if (op == HGX_ROOT_OTHER) {   // the first kept event was an Others entry: its value is the new Y
+            const std::array<uint8_t, 64>* old = find_root_other(c, ids);
+            if (old) {
+                std::memcpy(fr.y_id.data() + 32 * (size_t)p, old->data() + 32, 32);
+                fr.has_y[(size_t)p] = 1;
+            } else {
+                ids_ok = false;
+            }
+        }   // HGX_ROOT_Y: the old Root.Y stays
+    }
+    fr.ids_ok = ids_ok;
+}
+
 int32_t hgx_prune_to_frame(hgx_ctx* c, int64_t* old_gid, int64_t cap, int64_t* n_kept, hgx_error* err) {
     if (n_kept) *n_kept = 0;
     auto bad = [&](const char* why) {
@@ -1943,84 +2037,17 @@ int32_t hgx_prune_to_frame(hgx_ctx* c, int64_t* old_gid, int64_t cap, int64_t* n
         return HGX_ERR_KEY_NOT_FOUND;
     }
     DeviceGuard dg(c);
-    const int C = c->C;
-    // the cut and the new roots' Index and Round (Round(Root.X): from the round boundaries; -1 for
-    // an X outside the store or not yet divided, as hgx_get_frame has it)
-    std::vector<int32_t> cut((size_t)C, 0x7FFFFFFF), ri = c->root_index, rr = c->root_round;
-    std::vector<uint8_t> ye = c->root_y_ext;
+    std::vector<int32_t> cut, ri, rr;
     int64_t kept = 0;
-    const int32_t R = c->rh.R;
-    for (int p = 0; p < C; p++) {
-        const int32_t len = c->chain_len[(size_t)p];
-        if (len == 0) continue;   // LastFrom is the Root: it stays
-        int32_t k = len - 1;
-        if (lcr < R && c->rh.wflag[(size_t)lcr * C + p] == 2) k = c->rh.bm[(size_t)lcr * C + p];
-        if (k < 0 || k >= len) return bad("the round tables and the chains disagree");
-        cut[(size_t)p] = c->chain_base[(size_t)p] + k;
-        kept += len - k;
-        ri[(size_t)p] = cut[(size_t)p] - 1;
-        int32_t round = -1;
-        if (k > 0 && k - 1 < c->eng.len_div(p)) {
-            int32_t lo = 0, hi = R;   // the last r with bm[r] <= k - 1 (bm rows do not decrease)
-            while (lo < hi) {
-                const int32_t mid = (lo + hi) / 2;
-                if (c->rh.bm[(size_t)mid * C + p] <= k - 1) lo = mid + 1; else hi = mid;
-            }
-            round = lo - 1;
-        }
-        rr[(size_t)p] = round;
-    }
+    if (!frame_cut(c, lcr, cut, ri, rr, &kept)) return bad("the round tables and the chains disagree");
     hgx::Engine::PruneOut po;
     hipError_t e = c->eng.prune_stage(cut, kept, po);
     if (e != hipSuccess) return dev_err(err, e, "hgx_prune_to_frame");
     // ---- everything the new state needs, in locals; nothing is changed before it is complete ----
-    bool rooted = false;
-    for (int p = 0; p < C; p++) {
-        if (c->chain_len[(size_t)p] > 0) ye[(size_t)p] = po.root_op[(size_t)p] != -1 ? 1 : 0;
-        if (rr[(size_t)p] >= 0 || ye[(size_t)p]) rooted = true;
-    }
-    bool ids_ok = c->root_ids_known;
-    std::vector<uint8_t> x_id = c->root_x_id, y_id = c->root_y_id, has_x = c->root_has_x, has_y = c->root_has_y;
-    std::vector<std::array<uint8_t, 64>> others((size_t)po.n_others);
-    for (int64_t j = 0; j < po.n_others; j++) {
-        std::array<uint8_t, 64>& o = others[(size_t)j];
-        std::memcpy(o.data(), po.oth_key.data() + 32 * j, 32);
-        if (po.oth_op[(size_t)j] >= 0) {
-            std::memcpy(o.data() + 32, po.oth_pid.data() + 32 * j, 32);
-        } else {   // HGX_ROOT_OTHER before: the entry is carried over
-            const std::array<uint8_t, 64>* old = ids_ok ? find_root_other(c, o.data()) : nullptr;
-            if (old) std::memcpy(o.data() + 32, old->data() + 32, 32);
-            else { std::memset(o.data() + 32, 0, 32); ids_ok = false; }
-        }
-    }
-    std::sort(others.begin(), others.end(), [](const std::array<uint8_t, 64>& a, const std::array<uint8_t, 64>& b) {
-        return std::memcmp(a.data(), b.data(), 32) < 0;
-    });
-    for (int p = 0; p < C && ids_ok; p++) {
-        if (c->chain_len[(size_t)p] == 0) continue;   // the whole root stays
-        const uint8_t* ids = po.root_ids.data() + 96 * (size_t)p;
-        const int32_t sp = po.root_sp[(size_t)p], op = po.root_op[(size_t)p];
-        if (sp >= 0) {
-            std::memcpy(x_id.data() + 32 * (size_t)p, ids + 32, 32);
-            has_x[(size_t)p] = 1;
-        }   // -1: the old Root.X stays
-        if (op >= 0) {
-            std::memcpy(y_id.data() + 32 * (size_t)p, ids + 64, 32);
-            has_y[(size_t)p] = 1;
-        } else if (op == -1) {
-            has_y[(size_t)p] = 0;
-        } else if (op == HGX_ROOT_OTHER) {   // the first kept event was an Others entry: its value is the new Y
-            const std::array<uint8_t, 64>* old = find_root_other(c, ids);
-            if (old) {
-                std::memcpy(y_id.data() + 32 * (size_t)p, old->data() + 32, 32);
-                has_y[(size_t)p] = 1;
-            } else {
-                ids_ok = false;
-            }
-        }   // HGX_ROOT_Y: the old Root.Y stays
-    }
+    FrameRoots fr;
+    frame_roots(c, po, rr, fr);
     std::vector<uint8_t> keys((size_t)po.n_others * 32);
-    for (int64_t j = 0; j < po.n_others; j++) std::memcpy(keys.data() + 32 * j, others[(size_t)j].data(), 32);
+    for (int64_t j = 0; j < po.n_others; j++) std::memcpy(keys.data() + 32 * j, fr.others[(size_t)j].data(), 32);
     // the payloads restored by hgx_bootstrap follow their events (old gids ascend: a prefix has one)
     std::vector<int64_t> pl_off;
     std::vector<uint8_t> pl_blob;
@@ -2048,16 +2075,16 @@ int32_t hgx_prune_to_frame(hgx_ctx* c, int64_t* old_gid, int64_t cap, int64_t* n
     for (int64_t k = 0; k < kept && k < cap; k++) old_gid[k] = po.old_gid[(size_t)k];
     // ---- the destructive part: Reset with the frame's roots, then InsertEvent for the staged frame ----
     hgx::InsertOut out;
-    e = c->eng.prune_to_frame(rr, ye, po, out);
-    reset_host_state(c, ri.data(), rr, ye, rooted);
+    e = c->eng.prune_to_frame(rr, fr.y_ext, po, out);
+    reset_host_state(c, ri.data(), rr, fr.y_ext, fr.rooted);
     if (e != hipSuccess) return dev_err(err, e, "hgx_prune_to_frame");
     c->others_keys = std::move(keys);
-    c->root_ids_known = ids_ok;
-    c->root_x_id = std::move(x_id);
-    c->root_y_id = std::move(y_id);
-    c->root_has_x = std::move(has_x);
-    c->root_has_y = std::move(has_y);
-    c->root_others = std::move(others);
+    c->root_ids_known = fr.ids_ok;
+    c->root_x_id = std::move(fr.x_id);
+    c->root_y_id = std::move(fr.y_id);
+    c->root_has_x = std::move(fr.has_x);
+    c->root_has_y = std::move(fr.has_y);
+    c->root_others = std::move(fr.others);
     if (sync_root_ids(c) != hipSuccess) return dev_err(err, hipErrorUnknown, "hgx_prune_to_frame");
     hgx_error ie{};
     int64_t inserted = 0;
@@ -2069,6 +2096,116 @@ int32_t hgx_prune_to_frame(hgx_ctx* c, int64_t* old_gid, int64_t cap, int64_t* n
     if (rc != HGX_OK || inserted != kept) {   // the validation kernels re-checked the frame: a rejection is a bug
         set_err(err, HGX_ERR_PANIC, "hgx_prune_to_frame: frame event " + std::to_string(inserted) + " rejected: " + ie.msg);
         return HGX_ERR_PANIC;
+    }
+    return ok(err);
+}
+
+// ---- hgx_get_frame_bodies ----------------------------------------------
+// The serving half of a fast-forward: hgx_prune_to_frame's selection without its destructive part.
+// The cut and the roots are frame_cut / frame_roots, the staged columns Engine::prune_stage's, the
+// parents' ids k_frame_parent_ids', the bodies the store's gather through the staging's old gids.
+// Nothing is handed out before everything is on the host, so a refusal or a short capacity writes
+// no array, and the staging is disarmed on every way out.
+int32_t hgx_get_frame_bodies(hgx_ctx* c, hgx_frame_out* out, int64_t* n_events, int64_t* n_others, int64_t* n_tx,
+                             int64_t* n_bytes, hgx_error* err) {
+    const char* who = "hgx_get_frame_bodies";
+    if (n_events) *n_events = 0;
+    if (n_others) *n_others = 0;
+    if (n_tx) *n_tx = 0;
+    if (n_bytes) *n_bytes = 0;
+    auto bad = [&](const char* why) {
+        set_err(err, HGX_ERR_INVALID, std::string(who) + ": " + why);
+        return HGX_ERR_INVALID;
+    };
+    if (!c || !out || !n_events || !n_others || !n_tx || !n_bytes) return bad("bad arguments");
+    if (out->events_cap < 0 || out->others_cap < 0 || out->tx_cap < 0 || out->bytes_cap < 0) return bad("bad arguments");
+    if (c->G != 1) return bad("single-graph contexts only (roots need one graph)");
+    if (c->grp) return bad("not available on a chain-sharded context");
+    if (c->shard_world > 1) return bad("not available on a row-sharded context");
+    if (c->fo_open) return bad("a FindOrder is in progress (hgx_find_order_end first)");
+    if (!c->eng.ids_known) return bad("ids not known");
+    if (!c->root_ids_known) return bad("root ids not known");
+    const bool want_body = out->sig_r || out->tx_off || out->tx_bytes;
+    if (want_body && c->eng.bodies_state != hgx::kBodiesComplete) return bad("bodies not known");
+    const GraphState& s = c->gs[0];
+    const int32_t lcr = s.has_lcr ? s.lcr : 0;
+    if (!c->divided || lcr < 0 || lcr > s.last_round || s.round_events[(size_t)lcr] == 0) {   // Store.GetRound
+        set_err(err, HGX_ERR_KEY_NOT_FOUND, std::to_string(lcr) + ", Not Found");
+        return HGX_ERR_KEY_NOT_FOUND;
+    }
+    DeviceGuard dg(c);
+    const int C = c->C;
+    std::vector<int32_t> cut, ri, rr;
+    int64_t kept = 0;
+    if (!frame_cut(c, lcr, cut, ri, rr, &kept)) return bad("the round tables and the chains disagree");
+    struct Unstage {   // the staged-prune state is never left armed
+        hgx::Engine& eng;
+        ~Unstage() { eng.prune_unstage(); }
+    } unstage{c->eng};
+    hgx::Engine::PruneOut po;
+    hipError_t e = c->eng.prune_stage(cut, kept, po);
+    if (e != hipSuccess) return dev_err(err, e, who);
+    hgx::Engine::BodyPlan plan;
+    if (want_body) {
+        e = c->eng.frame_measure_bodies(plan);
+        if (e != hipSuccess) return dev_err(err, e, who);
+    }
+    *n_events = kept;
+    *n_others = po.n_others;
+    *n_tx = plan.n_tx;
+    *n_bytes = plan.n_bytes;
+    if (plan.too_large) {
+        set_err(err, HGX_ERR_CAPACITY, std::string(who) + ": the frame's bodies reach 4 GiB");
+        return HGX_ERR_CAPACITY;
+    }
+    const bool ev_cols = out->gid || out->creator || out->index || out->timestamp_ns || out->ntx || out->self_parent ||
+                         out->other_parent || out->id32 || out->sig_s || out->self_parent_id32 ||
+                         out->other_parent_id32 || out->parent_flags || out->sig_r;
+    const int64_t ev_cap = ev_cols ? out->events_cap : 0;
+    const int64_t oth_cap = out->others_event_id32 || out->others_parent_id32 ? out->others_cap : 0;
+    if (ev_cap < kept || oth_cap < po.n_others ||
+        (want_body && hgx::body_out_fits(plan.n_tx, plan.n_bytes, out->tx_off, out->tx_cap, out->tx_bytes, out->bytes_cap))) {
+        set_err(err, HGX_ERR_CAPACITY,
+                std::string(who) + ": events_cap / others_cap / tx_cap / bytes_cap too small (the four totals are set)");
+        return HGX_ERR_CAPACITY;
+    }
+    FrameRoots fr;
+    frame_roots(c, po, rr, fr);
+    bool missing = false;
+    e = c->eng.frame_fetch(&missing);
+    if (e != hipSuccess) return dev_err(err, e, who);
+    if (missing || !fr.ids_ok) {
+        set_err(err, HGX_ERR_PANIC, std::string(who) + ": a root id or Root.Others pair named by a stored parent is missing");
+        return HGX_ERR_PANIC;
+    }
+    if (want_body) {
+        const hgx::Engine::BodyOut bo{out->sig_r, nullptr, out->tx_off, out->tx_cap, out->tx_bytes, out->bytes_cap};
+        e = c->eng.bodies_fetch(plan, bo);
+        if (e != hipSuccess) return dev_err(err, e, who);
+    }
+    // ---- everything is on the host: hand it out ----
+    const hgx::Engine::FrameCols fc{out->gid, out->index, out->timestamp_ns, out->self_parent, out->other_parent,
+                                    out->creator, out->ntx, out->id32, out->sig_s, out->self_parent_id32,
+                                    out->other_parent_id32, out->parent_flags};
+    c->eng.frame_give(fc);
+    for (int p = 0; p < C; p++) {
+        const size_t z = (size_t)p;
+        if (out->root_index) out->root_index[z] = ri[z];
+        if (out->root_round) out->root_round[z] = rr[z];
+        if (out->root_has_x) out->root_has_x[z] = fr.has_x[z];
+        if (out->root_has_y) out->root_has_y[z] = fr.has_y[z];
+        if (out->root_x_id32) {
+            if (fr.has_x[z]) std::memcpy(out->root_x_id32 + 32 * z, fr.x_id.data() + 32 * z, 32);
+            else std::memset(out->root_x_id32 + 32 * z, 0, 32);
+        }
+        if (out->root_y_id32) {
+            if (fr.has_y[z]) std::memcpy(out->root_y_id32 + 32 * z, fr.y_id.data() + 32 * z, 32);
+            else std::memset(out->root_y_id32 + 32 * z, 0, 32);
+        }
+    }
+    for (int64_t j = 0; j < po.n_others; j++) {
+        if (out->others_event_id32) std::memcpy(out->others_event_id32 + 32 * j, fr.others[(size_t)j].data(), 32);
+        if (out->others_parent_id32) std::memcpy(out->others_parent_id32 + 32 * j, fr.others[(size_t)j].data() + 32, 32);
     }
     return ok(err);
 }

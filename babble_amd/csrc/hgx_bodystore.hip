@@ -336,6 +336,11 @@ hipError_t Engine::bodies_gather(const int64_t* gids_host, const int64_t* gids_d
     }
     if (body_out_fits(plan.n_tx, plan.n_bytes, out.tx_off, out.tx_cap, out.tx_bytes, out.bytes_cap)) return hipSuccess;
     *fit = kBodyFits;
+    return bodies_fetch(plan, out);
+}
+
+hipError_t Engine::bodies_fetch(const BodyPlan& plan, const BodyOut& out) {
+    const int64_t m = plan.m;
     if (m == 0) {
         if (out.tx_off) out.tx_off[0] = 0;
         return hipSuccess;

@@ -1125,7 +1125,8 @@ hipError_t Engine::prune_stage(const std::vector<int32_t>& cut, int64_t n_kept, 
     const size_t o_scan = take(Ez * 4), o_part = take(nparts * 4), o_cut = take(Cz * 4), o_first = take(Cz * 4),
                  o_cnt = take(8), o_cr = take(K * 4), o_idx = take(K * 4), o_sp = take(K * 4), o_op = take(K * 4),
                  o_ntx = take(K * 4), o_old = take(K * 4), o_ts = take(K * 8), o_hash = take(K * 32),
-                 o_S = take(K * 32), o_on = take(K * 4), o_oo = take(K * 4), o_ok = take(K * 32),
+                 o_S = take(K * 32), o_fsp = take(K * 32), o_fop = take(K * 32), o_fl = take(K), o_fail = take(4),
+                 o_on = take(K * 4), o_oo = take(K * 4), o_ok = take(K * 32),
                  o_opid = take(K * 32), o_rsp = take(Cz * 4), o_rop = take(Cz * 4), o_rid = take(Cz * 96);
     if (pr_buf.n < total) HGX_TRY(pr_buf.alloc(total));
     uint8_t* b = pr_buf.p;
@@ -1175,7 +1176,63 @@ hipError_t Engine::prune_stage(const std::vector<int32_t>& cut, int64_t n_kept, 
     pr_in.ts = a.st_ts; pr_in.hash = a.st_hash; pr_in.S = a.st_S; pr_in.ntx = a.st_ntx;
     pr_count = n_kept;
     pr_old_gid = a.old_gid;
+    pr_lay = PruneLayout{o_cr, o_idx, o_sp, o_op, o_ntx, o_old, o_ts, o_hash, o_S, o_fsp, o_fop, o_fl, o_fail, o_fail + 256};
     return hipSuccess;
+}
+
+// ---- hgx_get_frame_bodies (hgx_frame.hip) ----------------------------------
+// Behind prune_stage: one launch writes the parents' ids and flags behind the staged columns, and
+// the whole range (161 bytes per frame event and the fail word) comes back in ONE copy into
+// page-locked memory, then one synchronise.
+hipError_t Engine::frame_fetch(bool* missing) {
+    *missing = false;
+    if (pr_count < 0 || !ids_known) return hipErrorInvalidValue;
+    const size_t back = pr_lay.end - pr_lay.creator;
+    if (df_host_cap < back) {
+        if (df_host) (void)hipHostFree(df_host);
+        df_host = nullptr;
+        df_host_cap = 0;
+        const size_t want = std::max(back, (size_t)1 << 16);
+        HGX_TRY(hipHostMalloc((void**)&df_host, want, hipHostMallocDefault));
+        df_host_cap = want;
+    }
+    uint8_t* b = pr_buf.p;
+    FrameArgs a{};
+    a.E = E; a.n_kept = pr_count; a.C = C;
+    a.g_creator = g_creator.p; a.g_sp = g_sp.p; a.g_op = g_op.p; a.g_id = g_id.p;
+    a.old_gid = pr_old_gid;
+    a.root_tab = root_ids_set ? root_tab_d.p : nullptr;
+    a.root_pairs = root_ids_set && n_root_pairs > 0 ? root_pairs_d.p : nullptr;
+    a.n_pairs = a.root_pairs ? n_root_pairs : 0;
+    a.o_spid = b + pr_lay.spid; a.o_opid = b + pr_lay.opid; a.o_flags = b + pr_lay.flags;
+    a.fail = (uint32_t*)(b + pr_lay.fail);
+    HGX_TRY(hipMemsetAsync(b + pr_lay.fail, 0, 4, stream));
+    launch_frame_parent_ids(stream, a);
+    HGX_TRY(hipGetLastError());
+    HGX_TRY(hipMemcpyAsync(df_host, b + pr_lay.creator, back, hipMemcpyDeviceToHost, stream));
+    HGX_TRY(hipStreamSynchronize(stream));
+    uint32_t f = 0;
+    std::memcpy(&f, df_host + (pr_lay.fail - pr_lay.creator), 4);
+    *missing = f != 0;
+    return hipSuccess;
+}
+
+// the rows frame_fetch brought back, widened to the C ABI's columns
+void Engine::frame_give(const FrameCols& out) const {
+    const size_t K = (size_t)std::max<int64_t>(pr_count, 0);
+    auto at = [&](size_t off) { return df_host + (off - pr_lay.creator); };
+    auto widen = [&](int64_t* dst, size_t off) {
+        if (!dst) return;
+        const int32_t* s = (const int32_t*)at(off);
+        for (size_t k = 0; k < K; k++) dst[k] = s[k];
+    };
+    widen(out.gid, pr_lay.old); widen(out.index, pr_lay.index); widen(out.sp, pr_lay.sp); widen(out.op, pr_lay.op);
+    auto give = [&](void* dst, size_t off, size_t width) {
+        if (dst && K) std::memcpy(dst, at(off), width * K);
+    };
+    give(out.ts, pr_lay.ts, 8); give(out.creator, pr_lay.creator, 4); give(out.ntx, pr_lay.ntx, 4);
+    give(out.id, pr_lay.hash, 32); give(out.S, pr_lay.S, 32); give(out.spid, pr_lay.spid, 32);
+    give(out.opid, pr_lay.opid, 32); give(out.flags, pr_lay.flags, 1);
 }
 
 // A keeping context, between prune_stage and the commit: the kept events' bodies into new tables.

@@ -221,6 +221,8 @@ class Engine {
     hipError_t bodies_read(BodyTable which, int64_t lo, int64_t count, void* dst);
     hipError_t bodies_gather(const int64_t* gids_host, const int64_t* gids_dev64, const int32_t* gids_dev32, int64_t m,
                              const BodyOut& out, int64_t* n_tx, int64_t* n_bytes, BodyFit* fit);
+    // the second half of bodies_gather for a measured list that fits `out`: copy, one read-back, the arrays
+    hipError_t bodies_fetch(const BodyPlan& plan, const BodyOut& out);
     // hgx_prune_to_frame on a keeping context, behind prune_stage and before anything is dropped: the
     // kept events' bodies gathered into new tables, which prune_to_frame puts in place. On a failure
     // (hipErrorOutOfMemory; *too_large: the kept bodies reach 4 GiB) the context is as it was.
@@ -301,6 +303,22 @@ class Engine {
     hipError_t prune_stage(const std::vector<int32_t>& cut, int64_t n_kept, PruneOut& out);
     hipError_t prune_to_frame(const std::vector<int32_t>& root_round, const std::vector<uint8_t>& y_ext,
                               const PruneOut& st, InsertOut& out);
+    // hgx_get_frame_bodies (hgx_frame.hip), behind prune_stage: frame_fetch adds the
+    // parents' ids and flags (k_frame_parent_ids) to the staged columns and brings the whole range back
+    // in one copy into df_host; *missing: a root id or Others pair that must exist was not found (nothing
+    // may be handed out). frame_give then converts the rows into the caller's arrays (null = not
+    // wanted), frame_measure_bodies and bodies_fetch size and gather R and the transactions through the
+    // staging's old gids, and
+    // prune_unstage disarms the staging. None of them changes anything resident.
+    struct FrameCols {
+        int64_t *gid, *index, *ts, *sp, *op;
+        int32_t *creator, *ntx;
+        uint8_t *id, *S, *spid, *opid, *flags;
+    };
+    hipError_t frame_fetch(bool* missing);
+    void frame_give(const FrameCols& out) const;
+    hipError_t frame_measure_bodies(BodyPlan& plan) { return bodies_measure(nullptr, nullptr, pr_old_gid, pr_count, plan); }
+    void prune_unstage() { pr_count = -1; }
     // hgx_diff_wire (hgx_diff.hip): graph `graph`'s events with Index > known[creator]
     // in gid order, as wire columns (host pointers, null = not wanted; `rows` entries each are
     // filled, rows <= expect = the host plan's total; rows = 0 launches nothing). known / root_index:
@@ -554,6 +572,11 @@ class Engine {
     InsertIn pr_in{};
     int64_t pr_count = -1;   // events staged by prune_stage (-1: none)
     const int32_t* pr_old_gid = nullptr;   // ... their old gids (in pr_buf)
+    // the staged frame's columns as one range of pr_buf (byte offsets, [creator, end)), with room behind them for hgx_get_frame_bodies' parent ids, flags and fail word
+    struct PruneLayout {
+        size_t creator = 0, index = 0, sp = 0, op = 0, ntx = 0, old = 0, ts = 0, hash = 0, S = 0, spid = 0, opid = 0,
+               flags = 0, fail = 0, end = 0;
+    } pr_lay;
     // hgx_diff_wire: known | root_index, the per-2 048-gid partials, then a 256-byte header (the
     // device's total) and the output columns, 121 bytes per returned row; the header and the
     // columns come back in one copy into df_host (page-locked). Both grown on demand.

@@ -418,6 +418,24 @@ struct PruneArgs {
 };
 void launch_prune(hipStream_t s, const PruneArgs& a, uint32_t* scan_part);
 
+// hgx_get_frame_bodies (hgx_frame.hip): the ids of both parents of every staged frame
+// event (Go's Body.Parents), whether or not the parent is in the frame. old_gid: the staging's list of
+// launch_prune. root_tab / root_pairs: Engine::root_tab_d / root_pairs_d (root_tab null: no root has an id).
+struct FrameArgs {
+    int64_t E, n_kept;
+    int C;
+    const int32_t *g_creator, *g_sp, *g_op;
+    const uint8_t* g_id;
+    const int32_t* old_gid;        // [n_kept]
+    const uint8_t* root_tab;       // x_id [C][32] | y_id [C][32] | has_x [C] | has_y [C]
+    const uint64_t* root_pairs;    // [n_pairs][8] sorted: the key as 4 big-endian words, the value's 32 bytes
+    int64_t n_pairs;
+    uint8_t *o_spid, *o_opid;      // [n_kept][32], a zero row where the flag is clear
+    uint8_t* o_flags;              // [n_kept] bit 0: self-parent present, bit 1: other-parent present
+    uint32_t* fail;                // set to 1 (never cleared) when a root id or pair that must exist is missing
+};
+void launch_frame_parent_ids(hipStream_t s, const FrameArgs& a);
+
 // the scan's middle step alone: exclusive scan of nparts block totals in place (k_scan_top)
 void launch_scan_top(hipStream_t s, uint32_t* part, int nparts);
 

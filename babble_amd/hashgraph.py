@@ -680,6 +680,50 @@ class Hashgraph:
         self._call(lambda ctx, e: self.L.hgx_prune_to_frame(ctx, ptr(old), old.size, C.byref(nk), e))
         return old[:nk.value].copy()
 
+    def get_frame_bodies_raw(self, arrays: dict, events_cap=0, others_cap=0, tx_cap=0, bytes_cap=0):
+        """One bare hgx_get_frame_bodies call: arrays = {hgx_frame_out column: numpy array} (a column
+        left out is NULL). Returns (rc, error, (n_events, n_others, n_tx, n_bytes)); nothing is raised."""
+        out = _lib.hgx_frame_out()
+        for nm, a in arrays.items():
+            setattr(out, nm, ptr(a))
+        out.events_cap, out.others_cap, out.tx_cap, out.bytes_cap = events_cap, others_cap, tx_cap, bytes_cap
+        cnt = [C.c_int64() for _ in range(4)]
+        err = hgx_error()
+        rc = self.L.hgx_get_frame_bodies(self.ctx, C.byref(out), *[C.byref(x) for x in cnt], C.byref(err))
+        return rc, err, tuple(int(x.value) for x in cnt)
+
+    def GetFrameBodies(self, bodies: bool = True) -> dict:
+        """Hashgraph.GetFrame complete, for serving a fast-forward (hgx_get_frame_bodies): the frame
+        PruneToFrame would keep at this moment, and nothing changes. A sizing call, then the fill.
+        Returns the event columns of hgx_frame_out as numpy arrays in frame order (with bodies: sig_r,
+        tx_off and tx_bytes too), `roots` = dict(Index, Round, X, Y) per participant (None for "") and
+        `others` = the roots' Others pairs (event id, other-parent id) sorted by event id."""
+        C_ = self.n * self.G
+        spec = dict(_lib.FRAME_OUT_FIELDS)
+        want = [nm for nm in _lib.FRAME_EVENT_COLUMNS if bodies or nm != "sig_r"]
+        sizing = {"sig_r": np.zeros((1, 32), np.uint8)} if bodies else {}   # (a body column makes the body totals count)
+        rc, err, (ne, no, nt, nb) = self.get_frame_bodies_raw(sizing)
+        if rc not in (0, 103):
+            _lib.check(rc, err)
+        arr = {nm: np.zeros((C_,) + spec[nm][1], spec[nm][0]) for nm in _lib.FRAME_ROOT_COLUMNS}
+        arr.update({nm: np.zeros((max(1, no),) + spec[nm][1], spec[nm][0]) for nm in _lib.FRAME_OTHERS_COLUMNS})
+        arr.update({nm: np.zeros((max(1, ne),) + spec[nm][1], spec[nm][0]) for nm in want})
+        if bodies:
+            arr["tx_off"] = np.zeros(nt + 1, np.int64)
+            arr["tx_bytes"] = np.zeros(max(1, nb), np.uint8)
+        rc, err, got = self.get_frame_bodies_raw(arr, ne, no, nt, nb)
+        _lib.check(rc, err)
+        assert got == (ne, no, nt, nb)
+        res = {nm: arr[nm][:ne] for nm in want}
+        if bodies:
+            res["tx_off"], res["tx_bytes"] = arr["tx_off"], arr["tx_bytes"][:nb]
+        res["roots"] = [dict(Index=int(arr["root_index"][p]), Round=int(arr["root_round"][p]),
+                             X=arr["root_x_id32"][p].tobytes() if arr["root_has_x"][p] else None,
+                             Y=arr["root_y_id32"][p].tobytes() if arr["root_has_y"][p] else None) for p in range(C_)]
+        res["others"] = [(arr["others_event_id32"][j].tobytes(), arr["others_parent_id32"][j].tobytes())
+                         for j in range(no)]
+        return res
+
     def GetRootIds(self, participant: int) -> dict:
         """The 32-byte ids of the participant's Root.X and Root.Y (None for ""), known while every
         root traces back to genesis through PruneToFrame (hgx_get_root_ids)."""

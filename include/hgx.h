@@ -44,7 +44,7 @@ extern "C" {
                                  (hgx_p256_sign_batch, hgx_p256_public_keys, hgx_set_signing_keys,
                                  hgx_sign_insert_event_bodies), and with the event-id index
                                  (hgx_keep_id_index, hgx_id_index_state, hgx_find_events,
-                                 hgx_insert_events_by_id):
+                                 hgx_insert_events_by_id), and with hgx_get_frame_bodies (hgx_frame_out):
                                  purely additive, no existing entry or structure changed)
                               6: hgx_host_alloc / hgx_host_free (page-locked caller buffers);
                               5: hgx_events_packed (hgx_insert_events_packed, hgx_insert_and_run_packed,
@@ -586,6 +586,49 @@ int32_t hgx_get_root_others(hgx_ctx* ctx, uint8_t* event_id32, uint8_t* other_pa
 int32_t hgx_set_root_ids(hgx_ctx* ctx, const uint8_t* x_id32, const int32_t* has_x, const uint8_t* y_id32,
                          const int32_t* has_y, const uint8_t* others_event_id32, const uint8_t* others_parent_id32,
                          int64_t n_others, hgx_error* err);
+/* Hashgraph.GetFrame complete, for a peer's fast-forward (hashgraph.go:900-1006): the
+ * frame hgx_prune_to_frame would keep and the roots it would install at this moment, with ids and,
+ * on a context that keeps them, bodies. Nothing the caller can observe changes. Every array is
+ * host memory the caller owns; a NULL array is not written. */
+typedef struct {
+    /* the frame's Roots, n rows each (root.go:62-67) */
+    int32_t* root_index;  int32_t* root_round;
+    uint8_t* root_x_id32; int32_t* root_has_x;     /* 32 bytes per row; has = 0: "" (the row is zero) */
+    uint8_t* root_y_id32; int32_t* root_has_y;
+    /* Root.Others pairs sorted by event id, others_cap rows of 32 bytes each */
+    uint8_t* others_event_id32; uint8_t* others_parent_id32; int64_t others_cap;
+    /* the frame's Events in frame order (ascending gid), events_cap rows */
+    int64_t* gid;                                   /* the resident gid: old_gid of a prune run next */
+    int32_t* creator; int64_t* index; int64_t* timestamp_ns;
+    int32_t* ntx;                                   /* -1 = nil, as hgx_event_bodies */
+    int64_t* self_parent; int64_t* other_parent;    /* frame position, or -1 / HGX_ROOT_Y / HGX_ROOT_OTHER:
+                                                       the columns hgx_prune_to_frame would re-insert */
+    uint8_t* id32; uint8_t* sig_s;
+    /* Body.Parents as ids, whether or not the parent is in the frame; parent_flags bit 0 / bit 1 =
+     * the self- / other-parent is present, as hgx_insert_events_by_id reads them; the row of a clear
+     * flag is zero. A parent stored as a code reads the current roots: self-parent -1 -> the creator's
+     * Root.X id if it has one, HGX_ROOT_Y -> its Root.Y id, HGX_ROOT_OTHER -> the value of the
+     * Root.Others pair whose key is the event's id. */
+    uint8_t* self_parent_id32; uint8_t* other_parent_id32; uint8_t* parent_flags;
+    int64_t events_cap;
+    /* bodies (only on a context that keeps them): R, and the transactions as hgx_event_bodies has
+     * them (tx_off holds *n_tx + 1 offsets from 0, tx_cap counts transactions) */
+    uint8_t* sig_r; int64_t* tx_off; int64_t tx_cap; uint8_t* tx_bytes; int64_t bytes_cap;
+} hgx_frame_out;
+/* *n_events, *n_others, *n_tx, *n_bytes: the totals, always in full (the body totals are 0 unless one
+ * of sig_r, tx_off, tx_bytes is requested). All or nothing: a group of columns (events, Others,
+ * tx_off, tx_bytes) whose arrays are all NULL has capacity 0, and if events_cap < *n_events,
+ * others_cap < *n_others, tx_cap < *n_tx or bytes_cap < *n_bytes the call returns HGX_ERR_CAPACITY with
+ * the four totals set and no array written, the roots' included: an `out` of NULL arrays and zero
+ * capacities is the sizing call. The roots are what hgx_get_root_ids / hgx_get_root_others answer after
+ * the prune; a participant without events reports its whole current root. HGX_ERR_KEY_NOT_FOUND "<r>,
+ * Not Found" where hgx_get_frame gives it. HGX_ERR_INVALID "hgx_get_frame_bodies: <reason>", nothing
+ * written: NULL ctx, out or count pointer; a batch (G > 1), chain-sharded or row-sharded context; a
+ * FindOrder in progress; "ids not known"; "root ids not known" (a rooted context before
+ * hgx_set_root_ids); "bodies not known" when a body column is requested and hgx_bodies_state is not 1.
+ * HGX_ERR_PANIC when a root id or an Others pair that a stored code names is missing (a bug). */
+int32_t hgx_get_frame_bodies(hgx_ctx* ctx, hgx_frame_out* out, int64_t* n_events, int64_t* n_others,
+                             int64_t* n_tx, int64_t* n_bytes, hgx_error* err);
 
 /* ---- Hashgraph state (hashgraph.go:15-37) --------------------------------- */
 int64_t hgx_num_events(hgx_ctx* ctx);
